@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the ray-trace hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does what its headline figure needs and no more: set-up, W warm-up steps and 24 one-pass calls, the K timed steps, one untimed counting replay of the first
+min(K, 256) steps (the rays behind `value`), the outputs if `--dump-outputs` is given, the line.  `--full` adds everything else the line can carry:
+the single-kernel verification replay, one-pass and repeated-call timings, per-stage and build timings, the roofline block, the CPU
+baseline, and with N > 1 the `c5` block.  `--dump-outputs DIR` writes what the timed call left in the caller's buffers as DIR/accum.npy and
+DIR/image.npy (see dump_outputs); the inputs are the committed mesh and a fixed seed, so equal arguments give equal files.
 
 A "step" is one pass of the hot path over one full frame: every camera ray of the frame through
 ThreadWorker_Render's GPU equivalent (ray generation, tree traversal, triangle tests, shading,
@@ -16,12 +22,12 @@ after all passes).  Inputs are resident in HBM before the timed region starts.
 
 `python bench.py --gpus N` WITHOUT a launcher (WORLD_SIZE unset) starts its own N rank processes (python -m
 torch.distributed.run ... bench.py, before this process has touched a GPU), relays rank 0's line and exits with
-their status; launched under torch.distributed.run it is one rank.  With N > 1 and the default config the line also
+their status; launched under torch.distributed.run it is one rank.  With `--full`, N > 1 and the default config the line also
 carries a `c5` block (BASELINE configs[4]: the frame whose tiles can pay for 8 GPUs; its gather timed separately).
 `--rehearse`: every rank on GPU 0, gloo + a loopback stand-in under rtw_gather_rows -- a check of the N > 1 code path
 on a one-GPU box, not a measurement.
 
-Prints ONE JSON line (rank 0).  `roofline`: the path is LATENCY-bound (bound = "latency"); `frac` is the share of the
+Prints ONE JSON line (rank 0).  The rest of this paragraph is about `--full`.  `roofline`: the path is LATENCY-bound (bound = "latency"); `frac` is the share of the
 8 TB/s HBM roof that rocprofv3's counters saw (profiles/, stamped with the kernels' hash: printed only when the
 profile was taken on the build being timed), the algorithmic figures of SURVEY.md 8(d) are labelled extras; every
 fraction is computed from `ms_per_step`.  `cpu_baseline` times the reference's CPU path (oracle/_ref, the reference's
@@ -54,6 +60,7 @@ CONFIGS = {
 SEED = 12345
 TASK_ROWS = 10          # NumTaskRows, Src/RayTracerProgram.cpp:282
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: 8 TB/s spec
+COUNTED_PASSES = 256    # the untimed replay that counts rays covers at most this many of the K timed passes
 
 
 def procedural_torus_knot(path, segs=100, sides=6):
@@ -250,6 +257,25 @@ def profile_field(name, sha):
     return d, "profiles/%s (rocprofv3 run of this build's kernels %s; an earlier run, not this one)" % (name, sha)
 
 
+DUMP_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(dirname, accum_bits, argb, whole_accum):
+    """--dump-outputs: what the timed call left in the caller's two buffers after its last step, as float32 .npy files, one row per pixel:
+    accum.npy = the accumulator (R, G, B sums, and the sample count as a number: the buffer keeps it as an integer), image.npy = the R, G, B
+    bytes of the ARGB word (its alpha byte is always 255).  accum.npy is written only when this rank holds every row of it (N = 1, or
+    --gather-accum).  A frame whose files would pass DUMP_BYTES is cut down to a fixed, seeded choice of its pixels, the same rows in both files."""
+    os.makedirs(dirname, exist_ok=True)
+    n = len(argb)
+    keep = (DUMP_BYTES - 1024) // (12 + (16 if whole_accum else 0))        # bytes per pixel row in the two files; 1024 for their headers
+    rows = np.sort(np.random.default_rng(SEED).choice(n, keep, replace=False)) if n > keep else slice(None)
+    if whole_accum:
+        a = accum_bits.view(np.float32).copy()
+        a[:, 3] = accum_bits[:, 3].astype(np.float32)
+        np.save(os.path.join(dirname, "accum.npy"), a[rows])
+    np.save(os.path.join(dirname, "image.npy"), np.stack([(argb >> 16) & 255, (argb >> 8) & 255, argb & 255], 1).astype(np.float32)[rows])
+
+
 def spawn_ranks(args):
     """`python bench.py --gpus N` without a launcher: start the N ranks ourselves, BEFORE this process touches a GPU (it never does), the way the
     driver would (one process per GPU under torch.distributed.run, rendezvous on 127.0.0.1); relay rank 0's JSON line; exit with the children's status."""
@@ -368,10 +394,11 @@ class Bench:
         self.ctx.close()
 
 
-def measure(B, cfg, K, Wm, primary):
+def measure(B, cfg, K, Wm, primary, full):
     """W warm-up steps, then EXACTLY K steps (ONE rtw_render_passes call; with N > 1 followed by the one gather) between barriers, max over ranks;
-    rank 0 verifies the timed buffers against a pass-by-pass single-kernel replay and returns the block of figures (None on the other ranks).
-    primary: the config the line is about (all extras); else a compact block."""
+    rank 0 counts the rays of the first min(K, COUNTED_PASSES) steps in an untimed replay and returns the block of figures (None on the other ranks).
+    full: rank 0 also verifies the timed buffers against a pass-by-pass single-kernel replay and repeats the timed call.
+    primary: the config the line is about (with `full`, all extras); else a compact block."""
     torch, dist, R, args, ctx, dev, stream, rank, world = B.torch, B.dist, B.R, B.args, B.ctx, B.dev, B.stream, B.rank, B.world
     from raytracerwin_amd import sharding
     mesh, W, H, spp, depth, kind = CONFIGS[cfg]
@@ -433,6 +460,8 @@ def measure(B, cfg, K, Wm, primary):
         # the timed region, on every rank: a few milliseconds of the same kernels right before it.  (A stand-alone script with bench.py's sequence measured the
         # first 20-pass call after the set-up at 0.043 - 0.045 ms per pass by HIP events, after 40 such one-pass calls at 0.038 - 0.042, the calls that follow at
         # 0.037 - 0.039 either way; inside bench.py the one-shot figure still varies 0.039 - 0.044 from run to run -- see repeat_call_ms_per_step.)
+        # These 24 calls (4 ms) run without --full as well: they are part of the state the timed call starts from (without them a 192-step call measured
+        # 2 - 3 % slower); only --full prints their figures.
         single = None
         if primary:
             evs = [torch.cuda.Event(enable_timing=True) for _ in range(21)]
@@ -479,12 +508,15 @@ def measure(B, cfg, K, Wm, primary):
 
     res = None
     if rank == 0:
-        final_accum = accum.cpu().numpy().view(np.uint32).reshape(-1, 4).copy()
-        final_argb = argb.cpu().numpy().view(np.uint32).copy()
+        if full or (primary and args.dump_outputs):
+            final_accum = accum.cpu().numpy().view(np.uint32).reshape(-1, 4).copy()
+            final_argb = argb.cpu().numpy().view(np.uint32).copy()
+        if primary and args.dump_outputs:
+            dump_outputs(args.dump_outputs, final_accum, final_argb, world == 1 or not argb_only)
         # ---- untimed diagnostic (N = 1): the same call three more times, host clock around call + synchronise -- what a caller's loop sees from its second
         # call on (the timed call above is the FIRST of its shape after a shorter warm-up call: launch-size hints scaled from it, clocks just back from idle)
         repeat_ms_per_step = None
-        if world == 1:
+        if world == 1 and full:
             reps = []
             with torch.cuda.stream(stream):
                 for i in range(3):
@@ -497,24 +529,29 @@ def measure(B, cfg, K, Wm, primary):
         # ---- untimed: the same K passes once more on this GPU alone, pass by pass through the single kernel (pipeline 0, one thread per pixel):
         # the timed buffers must hold exactly these bits (N = 1 and N > 1 alike)
         fb2 = R.Framebuffer(ctx, W, H)
-        ctx.set_option("pipeline", 0)
-        for i in range(K):
-            R.ThreadWorker_Render(scene, fb2, 0, npix - 1, depth, None, i, spp, SEED)
-        a2 = fb2.read_float()
-        a2[:, 3] = a2[:, 3].astype(np.int32).view(np.float32)      # count back to int bits
-        b2 = fb2.resolve_argb()
-        ctx.set_option("pipeline", args.pipeline)
-        same_argb = bool((b2 == final_argb).all())
-        same_accum = bool((a2.view(np.uint32) == final_accum).all()) if not (world > 1 and argb_only) else None
-        verified = bool(same_argb and same_accum is not False)
-        # ---- work counters of the K timed passes as the timed pipeline runs them (one GPU, same grouping)
+        verified = None
+        if full:
+            ctx.set_option("pipeline", 0)
+            for i in range(K):
+                R.ThreadWorker_Render(scene, fb2, 0, npix - 1, depth, None, i, spp, SEED)
+            a2 = fb2.read_float()
+            a2[:, 3] = a2[:, 3].astype(np.int32).view(np.float32)      # count back to int bits
+            b2 = fb2.resolve_argb()
+            ctx.set_option("pipeline", args.pipeline)
+            same_argb = bool((b2 == final_argb).all())
+            same_accum = bool((a2.view(np.uint32) == final_accum).all()) if not (world > 1 and argb_only) else None
+            verified = bool(same_argb and same_accum is not False)
+        # ---- work counters of the timed passes as the timed pipeline runs them (one GPU, same grouping).  The counting kernels take some hundred times
+        # as long as the timed ones, so at most COUNTED_PASSES passes are replayed (the first ones) and a longer call's rays are those times K / Kc: a pass
+        # differs from the next only in its random decisions, and over 256 passes of a million rays each the sum is off by well under 1e-3 of itself
+        Kc = min(K, COUNTED_PASSES)
         ctx.stats_enable(True)
         ctx.stats_reset()
         fb2.clear()
-        scene.render_passes(fb2, TASK_ROWS, 0, 1, depth, None, 0, K, spp, SEED)
+        scene.render_passes(fb2, TASK_ROWS, 0, 1, depth, None, 0, Kc, spp, SEED)
         st = ctx.stats()
         ctx.stats_enable(False)
-        rays_total, cam_total = st["rays"], st["camera_rays"]
+        rays_total, cam_total = st["rays"] * (K / Kc), st["camera_rays"] * (K / Kc)
         res = {"workload": ("RayTracerProgram::SetupScene (4 spheres, capsule, ground plane, %s.obj) %dx%d %d spp depth %d, reference camera "
                             "(the reference's default scene and window; not a BASELINE config)" % (mesh, W, H, spp, depth)) if kind == "setup" else
                            "%s.obj %dx%d %d spp depth %d, %s, 1 mesh, reference camera (BASELINE configs[%s]%s)"
@@ -524,9 +561,9 @@ def measure(B, cfg, K, Wm, primary):
                "gather_ms": gather_ms, "rays_per_frame": rays_total / K, "camera_Mrays_per_s": cam_total / elapsed / 1e6,
                "verified": verified, "data": data, "depth": depth, "W": W, "H": H, "spp": spp, "kind": kind, "mesh_path": mesh_path,
                "commit_ms": commit_ms, "first_call_ms": first_call_ms, "second_call_ms": second_call_ms, "pipeline_run": ctx.last_pass_pipeline(),
-               "memory_bytes": memory_bytes, "group_passes": group_passes, "repeat_ms_per_step": repeat_ms_per_step}
-        if primary:
-            st_run_pass = {k: v / K for k, v in st.items()}
+               "memory_bytes": memory_bytes, "group_passes": group_passes, "repeat_ms_per_step": repeat_ms_per_step, "counted_passes": Kc}
+        if primary and full:
+            st_run_pass = {k: v / Kc for k, v in st.items()}
             # reference-faithful visit counts (un-pruned DFS order: what KdNode::TestRayIntersection visits) of ONE pass
             ctx.stats_enable(True)
             scene.set_prune(0)
@@ -599,8 +636,11 @@ def main():
                                                               "the reference writes out after its passes, the image")
     ap.add_argument("--no-c5", action="store_true", help="N>1 with the default config: leave out the `c5` block")
     ap.add_argument("--rehearse", action="store_true", help="N>1 on a ONE-GPU box: every rank on GPU 0, gloo + loopback transport (a check of the code path, not a measurement)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: leave out `cpu_baseline`")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the buffers the timed call filled, after its last step, as DIR/accum.npy and DIR/image.npy (float32)")
+    ap.add_argument("--full", action="store_true", help="also run and print everything beside the headline figure: verification replay, one-pass / repeated-call / stage / build "
+                                                        "timings, roofline block, CPU baseline, with N > 1 the `c5` block")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -612,28 +652,19 @@ def main():
     B = Bench(args)
     R, rank = B.R, B.rank
     K, Wm = args.steps, args.warmup
-    m = measure(B, args.config, K, Wm, True)
+    m = measure(B, args.config, K, Wm, True, args.full)
     c5 = None
-    if world > 1 and args.config == "c2" and not args.no_c5:
+    if args.full and world > 1 and args.config == "c2" and not args.no_c5:
         k5 = 4 * max(1, min(K, 8) // 4)             # whole 16-spp frames (four 4-spp passes each)
-        c5 = measure(B, "c5", k5, min(Wm, 4), False)
+        c5 = measure(B, "c5", k5, min(Wm, 4), False, True)
 
     if rank == 0:
         sha, version = kernels_sha(R)
         npix, spp, depth = m["W"] * m["H"], m["spp"], m["depth"]
         ms = m["ms_per_step"]
         sec = ms * 1e-3
-        # bytes per pass: SURVEY.md 8(d)'s weights on (a) the visits the reference's un-pruned walk makes, (b) the tests the timed kernels execute.
-        # The framebuffer term as EXECUTED: a group of passes reads and writes a pixel's accumulator once and stores its ARGB word once (the per-pass
-        # accumulate / divide / gamma arithmetic stays in registers), so 36 B per pixel and GROUP, i.e. 36 / passes-per-group per pixel-pass
         group = min(max(1, m["group_passes"]), K) if args.pipeline == 4 else 1
-        alg_ref = algorithmic_bytes(m["st_ref"], npix)
-        alg_run = algorithmic_bytes(m["st_run_pass"], npix / float(group))
-        tr, tr_src = profile_field("r03_traffic_%s.json" % args.config, sha) if world == 1 else (None, "N > 1: no per-rank profile")
-        ins, ins_src = profile_field("r03_%s_insts.json" % args.config, sha) if world == 1 else (None, "N > 1: no per-rank profile")
-        traffic = tr.get("hbm_bytes_per_pass") if tr else None
-        valu_per_pass = ins.get("valu_instructions_per_pass") if ins else None
-        hbm_gbs = (traffic / sec / 1e9) if traffic else None
+        # the plain line: the headline figure and what the timed call itself told about it
         result = {
             "metric": "Mrays/s (rays = closest-hit scene queries, primary + secondary) at %dx%d depth %d" % (m["W"], m["H"], depth),
             "value": m["value"], "unit": "Mrays/s", "n_gpus": world, "steps": K, "warmup": Wm,
@@ -642,20 +673,40 @@ def main():
             "config": {"workload": m["workload"],
                        "step": "one pass of the reference's sample loop over the whole frame; the K steps are ONE rtw_render_passes call, whose passes are rendered in groups "
                                "that share one set of launches: a pixel's pass colours are added to its accumulator one by one in pass order (in registers); its accumulator entry is written, and its "
-                               "ARGB word (divide + gamma of the accumulator after the group's last pass) computed and written, ONCE PER GROUP -- intermediate images are not materialised inside a call (single_pass_ms is "
-                               "the rate at which a caller can show every pass)",
+                               "ARGB word (divide + gamma of the accumulator after the group's last pass) computed and written, ONCE PER GROUP -- intermediate images are not materialised inside a call "
+                               "(--full: single_pass_ms is the rate at which a caller can show every pass)",
                        "sharding": "10-row tasks round-robin over ranks, one gather of the rows to rank 0 after the K passes",
                        "seed": SEED, "prune": args.prune, "pipeline": args.pipeline, "pipeline_run": m["pipeline_run"], "passes_per_group": group},
             "library": version,
             "camera_Mrays_per_s": m["camera_Mrays_per_s"],
+            "rays_per_frame": m["rays_per_frame"],
+            "rays_counted_over_passes": m["counted_passes"],
+            "timed_call_ms": {"wall_between_barriers": ms * K, "hip_events_around_the_call": m["render_ms_per_step_rank0"] * K, "host_inside_the_call": m["enqueue_ms"],
+                              "note": "the K steps are one asynchronous call: `host_inside_the_call` is how long the host took to enqueue its launches; a stall of that thread shows here and in both other figures"},
+            "full": args.full, "outputs": args.dump_outputs,
+        }
+        if B.rehearse:
+            result["rehearsal"] = "RTW_BENCH_REHEARSE=1: all %d ranks on GPU 0, gloo process group, loopback transport under rtw_gather_rows -- a check of the code path, not a measurement" % world
+        if world > 1:
+            result["gather_ms"] = m["gather_ms"]
+            result["gather"] = B.gather_kind + ("; ARGB only" if not args.gather_accum else "; accumulator + ARGB")
+    if rank == 0 and args.full:
+        # bytes per pass: SURVEY.md 8(d)'s weights on (a) the visits the reference's un-pruned walk makes, (b) the tests the timed kernels execute.
+        # The framebuffer term as EXECUTED: a group of passes reads and writes a pixel's accumulator once and stores its ARGB word once (the per-pass
+        # accumulate / divide / gamma arithmetic stays in registers), so 36 B per pixel and GROUP, i.e. 36 / passes-per-group per pixel-pass
+        alg_ref = algorithmic_bytes(m["st_ref"], npix)
+        alg_run = algorithmic_bytes(m["st_run_pass"], npix / float(group))
+        tr, tr_src = profile_field("r03_traffic_%s.json" % args.config, sha) if world == 1 else (None, "N > 1: no per-rank profile")
+        ins, ins_src = profile_field("r03_%s_insts.json" % args.config, sha) if world == 1 else (None, "N > 1: no per-rank profile")
+        traffic = tr.get("hbm_bytes_per_pass") if tr else None
+        valu_per_pass = ins.get("valu_instructions_per_pass") if ins else None
+        hbm_gbs = (traffic / sec / 1e9) if traffic else None
+        result.update({
             "nontrivial_Mrays_per_s": m["nontrivial"] / (ms * K * 1e-3) / 1e6,
             "nontrivial_rays_note": "rays that meet a shape's culling box: camera rays by pixel-centre direction (%d of %d per pass) + all secondary rays" % (m["nontrivial_cam"], npix * spp),
-            "rays_per_frame": m["rays_per_frame"],
             "verified_bit_identical_to_single_kernel_replay": m["verified"],
             "repeat_call_ms_per_step": m["repeat_ms_per_step"],
             "repeat_calls": 3 if m["repeat_ms_per_step"] else 0,
-            "timed_call_ms": {"wall_between_barriers": ms * K, "hip_events_around_the_call": m["render_ms_per_step_rank0"] * K, "host_inside_the_call": m["enqueue_ms"],
-                              "note": "the K steps are one asynchronous call: `host_inside_the_call` is how long the host took to enqueue its launches; a stall of that thread shows here and in both other figures"},
             "repeat_call_note": "the timed call again, three more times (best; host clock around call + synchronise): the timed figure above is the first call of its shape after a shorter warm-up",
             "single_pass_ms": m["single"]["median"] if m["single"] else None,
             "single_pass_note": ("median of 20 separate rtw_render_passes(n = 1) calls (min %.4f, max %.4f ms; HIP events around each call; launch-size hints primed by 4 such calls): "
@@ -694,12 +745,8 @@ def main():
                          "algorithmic_bytes_per_pass_executed": alg_run,
                          "algorithmic_bytes_per_pass_reference_order": alg_ref,
                          "counters_per_pass_reference_order": m["st_ref"], "counters_per_pass_as_run": m["st_run_pass"]},
-        }
-        if B.rehearse:
-            result["rehearsal"] = "RTW_BENCH_REHEARSE=1: all %d ranks on GPU 0, gloo process group, loopback transport under rtw_gather_rows -- a check of the code path, not a measurement" % world
+        })
         if world > 1:
-            result["gather_ms"] = m["gather_ms"]
-            result["gather"] = B.gather_kind + ("; ARGB only" if not args.gather_accum else "; accumulator + ARGB")
             result["gather_verified_bit_identical_to_1gpu"] = m["verified"]
             if c5 is not None:
                 result["c5"] = {"workload": c5["workload"], "value": c5["value"], "unit": "Mrays/s", "steps": c5["steps"], "warmup": c5["warmup"], "ms_per_step": c5["ms_per_step"],
@@ -712,6 +759,7 @@ def main():
                 result["cpu_baseline"] = cpu_baseline(m["mesh_path"], m["W"], m["H"], spp, depth, m["kind"], m["rays_per_frame"], args.cpu_budget)
             except Exception as e:      # the baseline is a reported extra, never the thing measured
                 result["cpu_baseline"] = {"value": None, "unit": "Mrays/s", "cores": None, "kind": "port", "sample": "failed: %r" % (e,)}
+    if rank == 0:
         print(json.dumps(result), flush=True)
     B.close()
 

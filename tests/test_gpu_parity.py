@@ -902,14 +902,14 @@ def test_bench_multirank_code_path_rehearsed_on_one_gpu(tmp_path):
 def test_bench_starts_its_own_ranks_when_no_launcher_did(tmp_path):
     """`python3 bench.py --gpus 2` with WORLD_SIZE unset -- the way the driver issues its N = 1 command -- must start the two rank processes itself (before it
     touches a GPU), relay rank 0's line and exit with their status.  Rehearsed on this one-GPU box (--rehearse: every rank on GPU 0, gloo, loopback transport
-    under rtw_gather_rows).  The line carries the C2 strong-scaling figures AND a `c5` block (BASELINE configs[4]) with its gather timed separately; both
+    under rtw_gather_rows).  With --full the line carries the C2 strong-scaling figures AND a `c5` block (BASELINE configs[4]) with its gather timed separately; both
     gathered images verified against the one-GPU replay."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--rehearse"], capture_output=True, text=True, timeout=900, env=env)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--rehearse", "--full"], capture_output=True, text=True, timeout=900, env=env)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout[-1500:], r.stderr[-3000:])
     d = json.loads(lines[0])
@@ -919,6 +919,36 @@ def test_bench_starts_its_own_ranks_when_no_launcher_did(tmp_path):
     c5 = d["c5"]
     assert "3840x2160" in c5["workload"] and c5["steps"] == 4 and c5["gather_verified_bit_identical_to_1gpu"] is True
     assert c5["gather_ms"] is not None and c5["ms_per_step"] > 0 and c5["value"] > 0
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_and_dumped_outputs(ctx, tmp_path):
+    """`bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR`, a plain run: the line has the headline fields and none of the --full extras, --steps
+    is the number of timed steps, and DIR holds the accumulator and the image of exactly those 3 passes (float32, one row per pixel), bit for bit what
+    the same 3 passes give pass by pass through the single kernel."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=300)
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
+    assert r.returncode == 0 and len(lines) == 1, (r.stdout[-1500:], r.stderr[-3000:])
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1 and d["full"] is False
+    assert d["unit"] == "Mrays/s" and d["higher_is_better"] is True and d["dtype"] == "f32" and d["ms_per_step"] > 0 and d["value"] > 0
+    assert abs(d["timed_call_ms"]["wall_between_barriers"] - 3 * d["ms_per_step"]) < 1e-9
+    for k in ("roofline", "cpu_baseline", "verified_bit_identical_to_single_kernel_replay", "single_pass_ms", "repeat_call_ms_per_step", "tree_and_bins_build_ms"):
+        assert k not in d, k
+    accum, image = np.load(str(out / "accum.npy")), np.load(str(out / "image.npy"))
+    W, H = 1920, 1080
+    assert accum.dtype == image.dtype == np.float32 and accum.shape == (W * H, 4) and image.shape == (W * H, 3)
+    assert sum(os.path.getsize(str(out / f)) for f in os.listdir(str(out))) <= 64 * 10 ** 6
+    ctx.set_option("pipeline", 0)
+    want_accum, want_argb = render_frame(ctx, gpu_scene(ctx, "TorusKnot", R.SurfaceMaterial_Diffuse((1, 1, 1))), W, H, 1, 4, False, 12345, 0, 3)
+    ctx.set_option("pipeline", DEFAULT_PIPELINE)
+    assert (bits(accum) == bits(want_accum)).all() and (accum[:, 3] == 3).all()
+    assert (image == np.stack([(want_argb >> 16) & 255, (want_argb >> 8) & 255, want_argb & 255], 1)).all()
 
 
 @pytest.mark.gpu

@@ -258,6 +258,38 @@ def test_analytic_shapes_keep_insertion_order_and_the_reference_culling_boxes(or
         s.AddShape(R.RSphere.Create((0, 0, 0), 1.0))        # committed
 
 
+def test_bench_output_dump_is_float32_bounded_and_the_same_rows_every_time(tmp_path):
+    """bench.py's dump_outputs: a 1080p frame is written whole (count as a number, R G B bytes of the ARGB word); a 4K frame is cut down to
+    a seeded choice of pixels that fits 64 MB, the same rows in both files and in every run; without the whole accumulator only the image."""
+    import bench
+    rng = np.random.default_rng(3)
+    for n, whole in ((1920 * 1080, True), (3840 * 2160, True), (3840 * 2160, False)):
+        acc = rng.random((n, 4), dtype=np.float32).view(np.uint32)
+        acc[:, 3] = 7
+        argb = rng.integers(0, 2 ** 32, n, dtype=np.uint32)
+        dirs = [str(tmp_path / ("d%d%d%d" % (n, whole, k))) for k in range(2)]
+        for d in dirs:
+            bench.dump_outputs(d, acc, argb, whole)
+        assert sorted(os.listdir(dirs[0])) == (["accum.npy", "image.npy"] if whole else ["image.npy"])
+        assert sum(os.path.getsize(os.path.join(dirs[0], f)) for f in os.listdir(dirs[0])) <= 64 * 10 ** 6
+        img = np.load(os.path.join(dirs[0], "image.npy"))
+        assert img.dtype == np.float32 and (bits(img) == bits(np.load(os.path.join(dirs[1], "image.npy")))).all()
+        rgb = np.stack([(argb >> 16) & 255, (argb >> 8) & 255, argb & 255], 1).astype(np.float32)
+        if n == 1920 * 1080:
+            assert (img == rgb).all()
+        else:
+            assert len(img) < n and len(img) * (28 if whole else 12) > 63 * 10 ** 6       # nearly all of the 64 MB is used
+        if whole:
+            a = np.load(os.path.join(dirs[0], "accum.npy"))
+            assert a.dtype == np.float32 and len(a) == len(img) and (a[:, 3] == 7).all()
+            assert (bits(a) == bits(np.load(os.path.join(dirs[1], "accum.npy")))).all()
+            if n == 1920 * 1080:
+                assert (bits(a[:, :3]) == acc[:, :3]).all()
+            else:       # the accumulator's rows are the image's rows: find the first one by its colour sums, the image row there must match
+                k = int(np.flatnonzero((acc[:, 0] == bits(a[:1, 0])) & (acc[:, 1] == bits(a[:1, 1])))[0])
+                assert (rgb[k] == img[0]).all()
+
+
 def _sanitizer_build():
     import subprocess
     here = os.path.join(ROOT, "tests", "cpu_emul")

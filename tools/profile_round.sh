@@ -1,5 +1,5 @@
 #!/bin/bash
-# tools/profile_round.sh TAG CONFIG [bench args...]  -- run ON THE GPU BOX (gpurun): rocprofv3 runs of `python3 bench.py --config CONFIG --no-cpu ...`
+# tools/profile_round.sh TAG CONFIG [bench args...]  -- run ON THE GPU BOX: rocprofv3 runs of `python3 bench.py --config CONFIG --full --no-cpu ...`
 #   1. --kernel-trace --stats                      -> per-kernel durations
 #   2. --pmc FETCH_SIZE      (own pass)            -> HBM read-side bytes per kernel
 #   3. --pmc WRITE_SIZE      (own pass)            -> HBM write-side bytes per kernel
@@ -15,7 +15,7 @@ cd /tmp && export TMPDIR=/tmp
 STEPS="--steps 20 --warmup 5"
 run() {  # name, rocprof args...
     local name=$1; shift
-    rocprofv3 "$@" --output-format csv -d $OUT/$name -o $name -- python3 $ROOTDIR/bench.py --config $CFG --no-cpu $STEPS "${BENCH_ARGS[@]}" > $OUT/$name.log 2>&1
+    rocprofv3 "$@" --output-format csv -d $OUT/$name -o $name -- python3 $ROOTDIR/bench.py --config $CFG --full --no-cpu $STEPS "${BENCH_ARGS[@]}" > $OUT/$name.log 2>&1
     grep -h '^{"metric"' $OUT/$name.log | tail -1 > $OUT/$name.bench.json || true
 }
 BENCH_ARGS=("$@")

@@ -1,5 +1,5 @@
 #!/bin/bash
-# tools/timeline.sh NAME [bench args]  -- ON THE GPU BOX: rocprofv3 --kernel-trace of `bench.py --no-cpu --steps 20 --warmup 5 [args]`, then the dispatches of
+# tools/timeline.sh NAME [bench args]  -- ON THE GPU BOX: rocprofv3 --kernel-trace of `bench.py --full --no-cpu --steps 20 --warmup 5 [args]`, then the dispatches of
 # the TIMED rtw_render_passes call in start order: start (us after the call's first kernel), duration, grid, kernel.
 set -e
 NAME=$1; shift
@@ -7,7 +7,7 @@ ROOTDIR=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOTDIR/gpurun_out/tl_$NAME
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $OUT -o $NAME -- python3 $ROOTDIR/bench.py --no-cpu --steps 20 --warmup 5 "$@" > $OUT/run.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $OUT -o $NAME -- python3 $ROOTDIR/bench.py --full --no-cpu --steps 20 --warmup 5 "$@" > $OUT/run.log 2>&1
 python3 - <<PY
 import csv, glob, re
 f = glob.glob("$OUT/**/*kernel_trace.csv", recursive=True)[0]
