@@ -222,6 +222,7 @@ public:
     rtw_framebuffer* Get() const { return Fb; }
     int bitmapWidth() const { return Width; }
     int bitmapHeight() const { return Height; }
+    void Clear() { RtwCheck(rtw_framebuffer_clear(Fb)); }      // accuBuffer[] and bitcolor[] back to zero (a new view starts a new accumulation)
     std::vector<Pixel> bitcolor() { std::vector<Pixel> p((size_t)Width * Height); RtwCheck(rtw_framebuffer_resolve_argb(Fb, p.data())); return p; }
     std::vector<float> accuBuffer() { std::vector<float> a((size_t)Width * Height * 4); RtwCheck(rtw_framebuffer_read_float(Fb, a.data())); return a; }
 private:
@@ -266,6 +267,16 @@ public:
         RtwCheck(rtw_ray_trace(Scene, ray, key, 1, MaxBounceTimes, InOption.UseBaseColor ? 1 : 0, seed, width, height, rgb));
         return RVec3(rgb[0], rgb[1], rgb[2]);
     }
+    // The camera of every later render call (the reference has one fixed camera: eye (0, 0, 7) looking down -z, the default here):
+    // a look-at pose and a vertical field of view in degrees; before or after the first render, and between render calls.
+    void SetCamera(const RVec3& eye, const RVec3& target, const RVec3& up, float vfovDegrees)
+    {
+        const float e[3] = { eye.x, eye.y, eye.z }, t[3] = { target.x, target.y, target.z }, u[3] = { up.x, up.y, up.z };
+        rtw_camera cam;
+        RtwCheck(rtw_camera_look_at(e, t, u, vfovDegrees, &cam));
+        RtwCheck(rtw_scene_set_camera(Scene, &cam));
+    }
+    rtw_camera GetCamera() const { rtw_camera cam; RtwCheck(rtw_scene_get_camera(Scene, &cam)); return cam; }
     void Commit() { if (!Committed) { RtwCheck(rtw_scene_commit(Scene)); Committed = true; } }
     rtw_scene* Get() { Commit(); return Scene; }
 private:

@@ -160,7 +160,33 @@ int rtw_scene_set_traversal(rtw_scene* scene, int mode);
  * leaf's own box (KdNode::Bounds of the leaf, Src/KdTree.cpp:37-60), level 1 / 2 = unions of 16 /
  * 256 consecutive leaves.  boxes6 = min.xyz, max.xyz per entry.  Returns the level's entry count. */
 int rtw_scene_mesh_flat(const rtw_scene* scene, int shape, int level, float* boxes6, int max_entries);
-/* Screen-space bins of the reference's fixed camera (Src/RayTracerProgram.cpp:133-165) for a
+/* ---- camera ----
+ * Pixel (x, y) of a width x height frame, sub-sample offset (ox, oy) (Src/RayTracerProgram.cpp:141-162: dx, dy, the quarter-pixel
+ * offsets and the two jitter draws) looks from `eye` along
+ *     v[k] = (right[k] * (dx + ox) + up[k] * (dy + oy)) + forward[k] * focal        (k = 0, 1, 2; every product and sum rounded on its own)
+ *     dir  = v * (1.0f / sqrtf(v.x * v.x + v.y * v.y + v.z * v.z)),   distance 1000.
+ * The reference's one camera is the default: eye (0, 0, 7), right (1, 0, 0), up (0, 1, 0), forward (0, 0, -1), focal 0.5; a scene
+ * whose camera equals it bit for bit renders through the fixed-pose kernels (the images, and the code, of a scene that never set one).
+ * The kernels use the struct's floats as given: the handedness of the basis is not checked, and a left-handed one (right = -cross(forward, up))
+ * renders the mirrored image without an error.  rtw_camera_look_at always returns a right-handed basis. */
+typedef struct { float eye[3], right[3], up[3], forward[3]; float focal; } rtw_camera;
+int rtw_camera_default(rtw_camera* out);
+/* forward = normalized(target - eye), right = normalized(cross(forward, up_hint)), up = cross(right, forward),
+ * focal = 0.25 / tan(vfov / 2) (the reference's 0.5 is vfov = 2 atan(0.5) ~ 53.13 degrees).  RTW_ERR_INVALID for a non-finite
+ * argument, vfov outside (0, 180), target == eye, or an up_hint parallel to forward. */
+int rtw_camera_look_at(const float eye[3], const float target[3], const float up_hint[3], float vfov_degrees, rtw_camera* out);
+/* The camera every render call of this scene uses from now on (NULL = the default).  Before or after commit, and between render
+ * calls: after commit it waits for the context's streams and drops the scene's cached screen bins and tile tables (they are rebuilt
+ * for the new pose on the next render call).  RTW_ERR_INVALID for non-finite values, focal <= 0, or a basis whose vectors are
+ * not unit length and mutually orthogonal to within 1e-4. */
+int rtw_scene_set_camera(rtw_scene* scene, const rtw_camera* cam);
+int rtw_scene_get_camera(const rtw_scene* scene, rtw_camera* out);
+/* The camera rays of n pixels (pixel = y * width + x) as the render kernels build them, jitter included: 7 floats each (origin,
+ * direction, distance), the layout rtw_trace_closest / rtw_ray_trace take.  Host only, needs no context. */
+int rtw_camera_rays(const rtw_camera* cam, int width, int height, const int32_t* pixels, int64_t n,
+                    int pass_index, int sub_sample, uint32_t seed, float* rays7);
+
+/* Screen-space bins of the scene's current camera (the reference's: Src/RayTracerProgram.cpp:133-165) for a
  * width x height frame cut into bin_w x bin_h pixel bins: CSR offsets (bins + 1) and, per bin, the
  * node indices (ascending) of the leaves whose triangle a camera ray of the bin's pixels could accept
  * (it faces the camera by the reference's own float test and its projection touches the bin).

@@ -415,6 +415,43 @@ class Framebuffer:
             pass
 
 
+class Camera(C.Structure):
+    """rtw_camera: a ray looks from `eye` along (right * (dx + ox) + up * (dy + oy)) + forward * focal, normalized."""
+    _fields_ = [("eye", C.c_float * 3), ("right", C.c_float * 3), ("up", C.c_float * 3), ("forward", C.c_float * 3), ("focal", C.c_float)]
+
+    @staticmethod
+    def default():
+        """The reference's one camera: eye (0, 0, 7), looking down -z, focal 0.5."""
+        cam = Camera()
+        _check(library().rtw_camera_default(C.byref(cam)))
+        return cam
+
+    @staticmethod
+    def look_at(eye, target, up=(0.0, 1.0, 0.0), vfov_degrees=53.13010235415598):
+        v3 = lambda v: (C.c_float * 3)(*[float(x) for x in v])  # noqa: E731
+        cam = Camera()
+        _check(library().rtw_camera_look_at(v3(eye), v3(target), v3(up), C.c_float(vfov_degrees), C.byref(cam)))
+        return cam
+
+    def as_array(self):
+        """the 13 floats: eye, right, up, forward, focal"""
+        return np.frombuffer(bytes(self), np.float32).copy()
+
+    def __eq__(self, other):
+        return isinstance(other, Camera) and bytes(self) == bytes(other)
+
+    __hash__ = None
+
+
+def camera_rays(camera, width, height, pixels, pass_index=0, sub_sample=0, seed=12345):
+    """The camera rays of `pixels` (y * width + x) as the render kernels build them: (n, 7) origin, direction, distance.  Host only."""
+    px = np.ascontiguousarray(pixels, np.int32).reshape(-1)
+    rays = np.zeros((len(px), 7), np.float32)
+    _check(library().rtw_camera_rays(None if camera is None else C.byref(camera), int(width), int(height), _p(px), C.c_int64(len(px)),
+                                     int(pass_index), int(sub_sample), C.c_uint32(seed), _p(rays)))
+    return rays
+
+
 class RayTracerScene:
     """Src/RayTracerScene.h:43-62.  AddShape() collects shapes; the first query commits."""
 
@@ -468,6 +505,15 @@ class RayTracerScene:
     def set_traversal(self, mode):
         _check(library().rtw_scene_set_traversal(self.h, int(mode)))
 
+    def set_camera(self, camera=None):
+        """The camera of every later render call (None = the reference's own); before or after commit, and between render calls."""
+        _check(library().rtw_scene_set_camera(self.h, None if camera is None else C.byref(camera)))
+
+    def get_camera(self):
+        cam = Camera()
+        _check(library().rtw_scene_get_camera(self.h, C.byref(cam)))
+        return cam
+
     def commit(self):
         if not self.committed:
             _check(library().rtw_scene_commit(self.h))
@@ -501,7 +547,7 @@ class RayTracerScene:
         return b
 
     def mesh_bins(self, width, height, bin_w, bin_h, shape=0):
-        """(offsets, entries) of the reference camera's screen bins, or None when the mesh gets none"""
+        """(offsets, entries) of the screen bins of the scene's current camera, or None when the mesh gets none"""
         self.commit()
         counts = np.zeros(2, np.int64)
         rc = library().rtw_scene_mesh_bins(self.h, shape, int(width), int(height), int(bin_w), int(bin_h), None, C.c_int64(0), None,

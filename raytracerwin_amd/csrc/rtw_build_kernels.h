@@ -345,21 +345,26 @@ __global__ void build_flat_up_kernel(const float* __restrict__ lower, int n_lowe
     for (int c = 0; c < 3; c++) { upper[(size_t)k * 6 + 2 * c] = lo[c]; upper[(size_t)k * 6 + 2 * c + 1] = hi[c]; }
 }
 
-// ---- screen-space bins of the reference's fixed camera, built on the device ---------------------------------------------------------
+// ---- screen-space bins of the scene's camera (rtw_types.h RtwBinsCam), built on the device ------------------------------------------
 // The host routine (scene_host.cpp build_bins) operation for operation, in double precision: a leaf is listed in the bins its triangle's
 // projection (grown by the jitter margin) touches when the triangle faces the camera by the reference's own float test.  Three passes:
 // count per bin, scan, fill (any order), then every bin's list sorted ascending = preorder.
-struct BinsGeom { int width, height, bin_w, bin_h, bx, by; double margin; };
+struct BinsGeom { int width, height, bin_w, bin_h, bx, by; double margin; RtwBinsCam cam; };     // margin = cam.margin (rtw_types.h rtw_bins_camera)
 
 // the bins of one leaf: calls f(bin) for every bin the leaf is listed in; returns false when the MESH gets no bins at all
 template <typename F>
 __device__ __forceinline__ bool bins_of_leaf(const RtwNode& nd, const RtwTri& t, const BinsGeom& g, F f)
 {
-    const double cx = (double)(g.width / 2), cy = (double)(g.height / 2), H = (double)g.height;
-    const double zmax = (double)nd.max_z - 7.0;
-    if (!(zmax < -0.01)) return false;                      // not wholly in front of the camera
+    const double cx = (double)(g.width / 2), cy = (double)(g.height / 2);
+    const RtwBinsCam& cam = g.cam;
+    for (int c = 0; c < 8; c++) {                           // a corner not in front of the eye: no bins for this mesh
+        const double qx = (double)((c & 1) ? nd.max_x : nd.min_x) - cam.eye[0], qy = (double)((c & 2) ? nd.max_y : nd.min_y) - cam.eye[1],
+                     qz = (double)((c & 4) ? nd.max_z : nd.min_z) - cam.eye[2];
+        const double depth = qx * cam.forward[0] + qy * cam.forward[1] + qz * cam.forward[2];
+        if (!(depth > 0.01)) return false;
+    }
     {
-        const float ox = 0.0f, oy = 0.0f, oz = 7.0f;
+        const float ox = cam.eye_f[0], oy = cam.eye_f[1], oz = cam.eye_f[2];
         const float d0 = t.nx * ox + t.ny * oy + t.nz * oz;
         const float d2 = d0 - t.d1;
         if (d2 < 0) return true;                            // faces away from every camera ray: listed nowhere
@@ -368,8 +373,10 @@ __device__ __forceinline__ bool bins_of_leaf(const RtwNode& nd, const RtwTri& t,
     double sx[3], sy[3];
     bool finite = true;
     for (int k = 0; k < 3; k++) {
-        const double qz = vz[k] - 7.0;
-        sx[k] = cx + H * vx[k] / qz; sy[k] = cy + H * vy[k] / qz;
+        const double qx = vx[k] - cam.eye[0], qy = vy[k] - cam.eye[1], qz = vz[k] - cam.eye[2];
+        const double depth = qx * cam.forward[0] + qy * cam.forward[1] + qz * cam.forward[2];
+        const double qr = qx * cam.right[0] + qy * cam.right[1] + qz * cam.right[2], qu = qx * cam.up[0] + qy * cam.up[1] + qz * cam.up[2];
+        sx[k] = cx - cam.k * qr / depth; sy[k] = cy - cam.k * qu / depth;
         finite = finite && sx[k] == sx[k] && sy[k] == sy[k] && fabs(sx[k]) < 1e12 && fabs(sy[k]) < 1e12;
     }
     if (!finite) return false;

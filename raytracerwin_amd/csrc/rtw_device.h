@@ -84,7 +84,7 @@ struct DeviceBuildOut {     // device memory, the caller's from here on (hipFree
     int n_nodes, tnodes_top, max_depth, flat_n[3], flat_pad[3];
 };
 int device_build_mesh(const DeviceBuildIn& in, int top_budget, DeviceBuildOut* out, hipStream_t stream);
-int device_build_bins(const RtwNode* d_nodes, const RtwTri* d_tris, int n_nodes, int width, int height, int bin_w, int bin_h,
+int device_build_bins(const RtwNode* d_nodes, const RtwTri* d_tris, int n_nodes, const RtwCamera& cam, int width, int height, int bin_w, int bin_h,
                       uint32_t** off_out, uint32_t** ent_out, uint32_t* h_off, int* has_bins, hipStream_t stream);
 #define RTW_PERSIST_CAND_BYTES (8 * 1024 * 4)   // candidate lists of a persistent trace block: RTW_GT_CAP_STAGED words x 1024 threads
 #define RTW_TNODES_TOP_BUDGET 3072 // records (32 B each) of a tree's upper levels a block of the ray-per-lane trace kernel stages in LDS: 96 KiB

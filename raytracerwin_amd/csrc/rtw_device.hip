@@ -753,8 +753,31 @@ __device__ f3 trace_path(const RtwSceneDev* __restrict__ sc, const TravCtx& tc, 
 }
 
 // ---- camera + resolve (Src/RayTracerProgram.cpp:131-188, Src/ColorBuffer.h:81-109) ---------------------------
-__device__ __forceinline__ Ray camera_ray(int width, int height, int pixel, int i, PathRng& rng)
+// CAM = false: the reference's fixed camera as constants (the code every default-pose frame has always run);
+// CAM = true: the scene's camera from the launch parameters (rtw_types.h RtwCamera: every product and every sum rounded on its own)
+template <bool CAM>
+__device__ __forceinline__ Ray camera_ray_from(const RtwCamera& c, float a, float b)
 {
+    Ray r;
+    if (CAM) {
+        r.o = mk(c.eye[0], c.eye[1], c.eye[2]);
+        r.d = normalized(mk((c.right[0] * a + c.up[0] * b) + c.forward[0] * c.focal,
+                            (c.right[1] * a + c.up[1] * b) + c.forward[1] * c.focal,
+                            (c.right[2] * a + c.up[2] * b) + c.forward[2] * c.focal));
+    } else {
+        r.o = mk(0, 0, 7.0f);
+        r.d = normalized(mk(a, b, -0.5f));
+    }
+    r.dist = 1000.0f;
+    return r;
+}
+template <bool CAM>
+__device__ __forceinline__ f3 camera_eye(const RtwCamera& c) { return CAM ? mk(c.eye[0], c.eye[1], c.eye[2]) : mk(0, 0, 7.0f); }
+
+template <bool CAM>
+__device__ __forceinline__ Ray camera_ray(const RtwRenderParams& p, int pixel, int i, PathRng& rng)
+{
+    const int width = p.width, height = p.height;
     const float aspect = (float)width / (float)height;
     const int x = pixel % width, y = pixel / width;
     const float dx = -(float)(x - width / 2) / (width * 2) * aspect;
@@ -765,14 +788,11 @@ __device__ __forceinline__ Ray camera_ray(int width, int height, int pixel, int 
     float oy = (i & 2) ? inv_pixel_radius : 0.0f;
     ox += (rng.random() - 0.5f) * offset_radius;
     oy += (rng.random() - 0.5f) * offset_radius;
-    Ray r;
-    r.o = mk(0, 0, 7.0f);
-    r.d = normalized(mk(dx + ox, dy + oy, -0.5f));
-    r.dist = 1000.0f;
-    return r;
+    return camera_ray_from<CAM>(p.cam, dx + ox, dy + oy);
 }
 
 // the same ray from the host's per-column / per-row tables (tiled pipelines): dx and dy hold exactly the floats above
+template <bool CAM>
 __device__ __forceinline__ Ray camera_ray_xy(const RtwRenderParams& p, int x, int y, int i, PathRng& rng)
 {
     const float dx = p.cam_dx[x], dy = p.cam_dy[y];
@@ -782,11 +802,7 @@ __device__ __forceinline__ Ray camera_ray_xy(const RtwRenderParams& p, int x, in
     float oy = (i & 2) ? inv_pixel_radius : 0.0f;
     ox += (rng.random() - 0.5f) * offset_radius;
     oy += (rng.random() - 0.5f) * offset_radius;
-    Ray r;
-    r.o = mk(0, 0, 7.0f);
-    r.d = normalized(mk(dx + ox, dy + oy, -0.5f));
-    r.dist = 1000.0f;
-    return r;
+    return camera_ray_from<CAM>(p.cam, dx + ox, dy + oy);
 }
 
 // 8-bit value of MakePixelColor(LinearToGamma(c)) for one channel: the largest k with thr[k] <= c.
@@ -890,7 +906,7 @@ __device__ __forceinline__ int work_to_pixel(const RtwRenderParams& p, int wi)
 }
 
 // ---- kernels -----------------------------------------------------------------------------------------
-template <bool STATS>
+template <bool STATS, bool CAM>
 __global__ __launch_bounds__(256) void render_kernel(const RtwSceneDev* __restrict__ sc, float4* __restrict__ accum,
                                                      uint32_t* __restrict__ argb, float4* __restrict__ ws, RtwRenderParams p)
 {
@@ -908,7 +924,7 @@ __global__ __launch_bounds__(256) void render_kernel(const RtwSceneDev* __restri
         f3 c = mk(0, 0, 0);
         for (int i = 0; i < p.sub_samples; i++) {
             PathRng rng; rng_init(rng, p.seed, phase, (uint64_t)npix, (uint32_t)pixel, (uint32_t)p.pass_index, (uint32_t)i);
-            const Ray ray = camera_ray(p.width, p.height, pixel, i, rng);
+            const Ray ray = camera_ray<CAM>(p, pixel, i, rng);
             if (STATS) ct.cams++;
             c = c + trace_path<STATS>(sc, tc, ray, p.max_bounce, p.preview != 0, rng, ct, lv);
         }
@@ -1229,8 +1245,13 @@ int launch_render(const RtwSceneDev* sc, void* accum, void* argb, void* ws, cons
     if (p.count <= 0) return 0;
     const int block = 256;
     const int grid = (p.count + block - 1) / block;
-    if (stats) hipLaunchKernelGGL(render_kernel<true>, dim3(grid), dim3(block), 0, stream, sc, (float4*)accum, (uint32_t*)argb, (float4*)ws, p);
-    else hipLaunchKernelGGL(render_kernel<false>, dim3(grid), dim3(block), 0, stream, sc, (float4*)accum, (uint32_t*)argb, (float4*)ws, p);
+    if (p.cam_general) {
+        if (stats) hipLaunchKernelGGL((render_kernel<true, true>), dim3(grid), dim3(block), 0, stream, sc, (float4*)accum, (uint32_t*)argb, (float4*)ws, p);
+        else hipLaunchKernelGGL((render_kernel<false, true>), dim3(grid), dim3(block), 0, stream, sc, (float4*)accum, (uint32_t*)argb, (float4*)ws, p);
+    } else {
+        if (stats) hipLaunchKernelGGL((render_kernel<true, false>), dim3(grid), dim3(block), 0, stream, sc, (float4*)accum, (uint32_t*)argb, (float4*)ws, p);
+        else hipLaunchKernelGGL((render_kernel<false, false>), dim3(grid), dim3(block), 0, stream, sc, (float4*)accum, (uint32_t*)argb, (float4*)ws, p);
+    }
     return (int)hipGetLastError();
 }
 
@@ -1302,7 +1323,8 @@ int launch_render_pipeline(const RtwSceneDev* sc, void* accum, void* argb, void*
                 const int sky_jobs = p.n_jobs - tune.sky_job0;
                 int sgrid = (sky_jobs + 3) / 4;
                 if (sgrid > tune.cu_count * 64) sgrid = tune.cu_count * 64;
-                hipLaunchKernelGGL(primary_sky_kernel, dim3(sgrid), dim3(block), 0, tune.aux_stream, tune.gamma_thr, (float4*)accum, (uint32_t*)argb, p, tune.sky_job0);
+                if (p.cam_general) hipLaunchKernelGGL(primary_sky_kernel<true>, dim3(sgrid), dim3(block), 0, tune.aux_stream, tune.gamma_thr, (float4*)accum, (uint32_t*)argb, p, tune.sky_job0);
+                else hipLaunchKernelGGL(primary_sky_kernel<false>, dim3(sgrid), dim3(block), 0, tune.aux_stream, tune.gamma_thr, (float4*)accum, (uint32_t*)argb, p, tune.sky_job0);
                 if (tune.do_join) (void)hipEventRecord(tune.join_event, tune.aux_stream);
                 else if (tune.aux_unjoined) *tune.aux_unjoined = true;
                 ph.n_jobs = tune.sky_job0;
@@ -1310,13 +1332,17 @@ int launch_render_pipeline(const RtwSceneDev* sc, void* accum, void* argb, void*
         }
         const int jobs_grid = ph.tile_order ? (ph.n_jobs + 3) / 4 : grid;        // a wave per job (a tile, or a tile's sub-sample); else waves take jobs in turn
         const int pgrid = jobs_grid < tune.cu_count * 64 ? jobs_grid : tune.cu_count * 64;
-        if (tune.has_analytic) {
-            if (stats) hipLaunchKernelGGL((primary_bins_kernel<true, true>), dim3(pgrid), dim3(block), 0, stream, sc, (float4*)accum, (uint32_t*)argb, pb, ph);
-            else hipLaunchKernelGGL((primary_bins_kernel<false, true>), dim3(pgrid), dim3(block), 0, stream, sc, (float4*)accum, (uint32_t*)argb, pb, ph);
-        } else {
-            if (stats) hipLaunchKernelGGL((primary_bins_kernel<true, false>), dim3(pgrid), dim3(block), 0, stream, sc, (float4*)accum, (uint32_t*)argb, pb, ph);
-            else hipLaunchKernelGGL((primary_bins_kernel<false, false>), dim3(pgrid), dim3(block), 0, stream, sc, (float4*)accum, (uint32_t*)argb, pb, ph);
-        }
+        // (CAM_: the general-camera instantiation; the default pose keeps the fixed-pose one)
+#define RTW_PRIMARY_BINS(CAM_) do { \
+        if (tune.has_analytic) { \
+            if (stats) hipLaunchKernelGGL((primary_bins_kernel<true, true, CAM_>), dim3(pgrid), dim3(block), 0, stream, sc, (float4*)accum, (uint32_t*)argb, pb, ph); \
+            else hipLaunchKernelGGL((primary_bins_kernel<false, true, CAM_>), dim3(pgrid), dim3(block), 0, stream, sc, (float4*)accum, (uint32_t*)argb, pb, ph); \
+        } else { \
+            if (stats) hipLaunchKernelGGL((primary_bins_kernel<true, false, CAM_>), dim3(pgrid), dim3(block), 0, stream, sc, (float4*)accum, (uint32_t*)argb, pb, ph); \
+            else hipLaunchKernelGGL((primary_bins_kernel<false, false, CAM_>), dim3(pgrid), dim3(block), 0, stream, sc, (float4*)accum, (uint32_t*)argb, pb, ph); \
+        } } while (0)
+        if (p.cam_general) RTW_PRIMARY_BINS(true); else RTW_PRIMARY_BINS(false);
+#undef RTW_PRIMARY_BINS
     }
     if (tune.timing) (void)hipEventRecord(tune.timing[1], stream);
     auto items_of = [&](int round) {
@@ -1404,7 +1430,8 @@ int launch_render_group(const RtwSceneDev* sc, void* accum, void* argb, void* wo
             gs.first_pass = tune.sky_first_pass; gs.n_passes = tune.sky_passes;
             int sgrid = (gs.n_sky + 3) / 4;
             if (sgrid > tune.cu_count * tune.sky_blocks) sgrid = tune.cu_count * tune.sky_blocks;
-            hipLaunchKernelGGL(gsky_kernel, dim3(sgrid), dim3(256), 0, stream, tune.gamma_thr, (float4*)accum, (uint32_t*)argb, gs);
+            if (p.cam_general) hipLaunchKernelGGL(gsky_kernel<true>, dim3(sgrid), dim3(256), 0, stream, tune.gamma_thr, (float4*)accum, (uint32_t*)argb, gs);
+            else hipLaunchKernelGGL(gsky_kernel<false>, dim3(sgrid), dim3(256), 0, stream, tune.gamma_thr, (float4*)accum, (uint32_t*)argb, gs);
         }
         return (int)hipGetLastError();
     }
@@ -1429,7 +1456,8 @@ int launch_render_group(const RtwSceneDev* sc, void* accum, void* argb, void* wo
         }
         int sgrid = (g.n_sky + 3) / 4;
         if (sgrid > tune.cu_count * tune.sky_blocks) sgrid = tune.cu_count * tune.sky_blocks;
-        hipLaunchKernelGGL(gsky_kernel, dim3(sgrid), dim3(256), 0, ss, tune.gamma_thr, (float4*)accum, (uint32_t*)argb, gs);
+        if (p.cam_general) hipLaunchKernelGGL(gsky_kernel<true>, dim3(sgrid), dim3(256), 0, ss, tune.gamma_thr, (float4*)accum, (uint32_t*)argb, gs);
+        else hipLaunchKernelGGL(gsky_kernel<false>, dim3(sgrid), dim3(256), 0, ss, tune.gamma_thr, (float4*)accum, (uint32_t*)argb, gs);
         if (forked) {
             if (tune.do_join) (void)hipEventRecord(tune.join_event, tune.aux_stream);
             else if (tune.aux_unjoined) *tune.aux_unjoined = true;
@@ -1442,13 +1470,16 @@ int launch_render_group(const RtwSceneDev* sc, void* accum, void* argb, void* wo
             const int ppw = (g.primary_passes > 1 && g.primary_passes * p.sub_samples <= 4) ? g.primary_passes : 1;        // as the kernel reads it
             const long long waves = (long long)g.n_jobs * ((g.n_passes + ppw - 1) / ppw);
             const unsigned pgrid = (unsigned)((waves + 3) / 4);
-            if (tune.has_analytic) {
-                if (stats) hipLaunchKernelGGL((gprimary_kernel<true, true>), dim3(pgrid), dim3(256), 0, stream, sc, gb, g);
-                else hipLaunchKernelGGL((gprimary_kernel<false, true>), dim3(pgrid), dim3(256), 0, stream, sc, gb, g);
-            } else {
-                if (stats) hipLaunchKernelGGL((gprimary_kernel<true, false>), dim3(pgrid), dim3(256), 0, stream, sc, gb, g);
-                else hipLaunchKernelGGL((gprimary_kernel<false, false>), dim3(pgrid), dim3(256), 0, stream, sc, gb, g);
-            }
+#define RTW_GPRIMARY(CAM_) do { \
+            if (tune.has_analytic) { \
+                if (stats) hipLaunchKernelGGL((gprimary_kernel<true, true, CAM_>), dim3(pgrid), dim3(256), 0, stream, sc, gb, g); \
+                else hipLaunchKernelGGL((gprimary_kernel<false, true, CAM_>), dim3(pgrid), dim3(256), 0, stream, sc, gb, g); \
+            } else { \
+                if (stats) hipLaunchKernelGGL((gprimary_kernel<true, false, CAM_>), dim3(pgrid), dim3(256), 0, stream, sc, gb, g); \
+                else hipLaunchKernelGGL((gprimary_kernel<false, false, CAM_>), dim3(pgrid), dim3(256), 0, stream, sc, gb, g); \
+            } } while (0)
+            if (p.cam_general) RTW_GPRIMARY(true); else RTW_GPRIMARY(false);
+#undef RTW_GPRIMARY
         }
         if (tune.timing) (void)hipEventRecord(tune.timing[1], stream);
         auto blocks_for = [&](int list_round) {      // blocks of 256 lanes for the paths of list `list_round` (a grid-stride loop takes any excess)
@@ -1681,14 +1712,15 @@ int device_build_mesh(const DeviceBuildIn& in, int top_budget, DeviceBuildOut* o
 }
 // Screen bins of one mesh on the device.  *off_out (n_bins + 1 offsets) and *ent_out are the caller's (hipFree); h_off receives the offsets
 // (the host sorts the tiles by list length).  Returns 0 and *has_bins = 0 when the mesh gets no bins (as build_bins returns false).
-int device_build_bins(const RtwNode* d_nodes, const RtwTri* d_tris, int n_nodes, int width, int height, int bin_w, int bin_h,
+int device_build_bins(const RtwNode* d_nodes, const RtwTri* d_tris, int n_nodes, const RtwCamera& cam, int width, int height, int bin_w, int bin_h,
                       uint32_t** off_out, uint32_t** ent_out, uint32_t* h_off, int* has_bins, hipStream_t stream)
 {
     BinsGeom g; g.width = width; g.height = height; g.bin_w = bin_w; g.bin_h = bin_h;
     g.bx = (width + bin_w - 1) / bin_w; g.by = (height + bin_h - 1) / bin_h;
-    g.margin = 1.0 + 1.25 * (double)height / (2.0 * (double)width);
+    g.cam = rtw_bins_camera(cam, width, height); g.margin = g.cam.margin;
     const int n_bins = g.bx * g.by;
     *off_out = nullptr; *ent_out = nullptr; *has_bins = 0;
+    if (!g.cam.ok) return 0;
     TempBufs tmp;
     uint32_t *d_counts, *d_flag;
     RTW_HIP_OK(tmp.get(&d_counts, (size_t)n_bins)); RTW_HIP_OK(tmp.get(&d_flag, 1));

@@ -224,6 +224,7 @@ __device__ __forceinline__ void group_save_state(const GroupBufs& gb, uint32_t s
 }
 
 // ---- sky-only tiles: K passes per pixel with the accumulator entry in registers ----------------------------------------------
+template <bool CAM>
 __global__ __launch_bounds__(256) void gsky_kernel(const float* __restrict__ gamma_thr, float4* __restrict__ accum, uint32_t* __restrict__ argb, RtwGroupParams g)
 {
     __shared__ float thr[256];
@@ -247,7 +248,7 @@ __global__ __launch_bounds__(256) void gsky_kernel(const float* __restrict__ gam
             f3 csum = mk(0, 0, 0);
             for (int i = 0; i < p.sub_samples; i++) {
                 PathRng rng; rng_init(rng, p.seed, phase, (uint64_t)npix, (uint32_t)pixel, (uint32_t)(g.first_pass + k), (uint32_t)i);
-                const Ray ray = camera_ray_xy(p, px, py, i, rng);
+                const Ray ray = camera_ray_xy<CAM>(p, px, py, i, rng);
                 const f3 si = p.max_bounce != 0 ? sky_color(ray.d.y) : mk(0, 0, 0);       // RayTrace(.., 0) is black (Src/RayTracerScene.cpp:39)
                 csum = csum + si;
             }
@@ -325,7 +326,7 @@ __device__ __forceinline__ void bins_walk_rays(const RtwShapeDev& sh, const uint
 
 __device__ __forceinline__ float pick4(int r, float a, float b, float c, float d) { return r == 0 ? a : (r == 1 ? b : (r == 2 ? c : d)); }
 
-template <bool STATS, bool AN>
+template <bool STATS, bool AN, bool CAM>
 #ifndef RTW_GPRIMARY_MINB
 #define RTW_GPRIMARY_MINB 3      // measured in one session: 3 blocks of 256 per CU (<= 168 VGPRs) makes the primary kernel 13 % faster on unitychan (C4 0.343 -> 0.315 ms per pass), neutral on TorusKnot; 4 blocks (round 3, 128 VGPRs): C2 +3 %, C3 +4 % slower
 #endif
@@ -386,7 +387,7 @@ __global__ __launch_bounds__(256, RTW_GPRIMARY_MINB) void gprimary_kernel(const 
                 if (r < nr) {
                     const uint32_t po = (uint32_t)r / nsub, i = only_sample >= 0 ? (uint32_t)only_sample : (uint32_t)r - po * nsub;
                     PathRng rng; rng_init(rng, p.seed, phase, (uint64_t)npix, (uint32_t)pixel, (uint32_t)g.first_pass + kbase + po, i);
-                    const Ray ray = camera_ray_xy(p, px, py, (int)i, rng);
+                    const Ray ray = camera_ray_xy<CAM>(p, px, py, (int)i, rng);
                     float t0, t1;
                     w_d[r] = ray.d; w_cur[r] = ray.dist;
                     w_act[r] = live && slab_exact(ray, sh.bmin[0], sh.bmin[1], sh.bmin[2], sh.bmax[0], sh.bmax[1], sh.bmax[2], t0, t1);
@@ -395,7 +396,7 @@ __global__ __launch_bounds__(256, RTW_GPRIMARY_MINB) void gprimary_kernel(const 
             }
             if (__ballot(!all_tame) == 0ull) {
                 shared_walk = true;
-                bins_walk_rays<STATS>(sh, p.bins[0].off, p.bins[0].ent, bin, lane, nr, prune, mk(0, 0, 7.0f), w_d, w_act, w_cur, w_pos, w_slot, w_any, ct);
+                bins_walk_rays<STATS>(sh, p.bins[0].off, p.bins[0].ent, bin, lane, nr, prune, camera_eye<CAM>(p.cam), w_d, w_act, w_cur, w_pos, w_slot, w_any, ct);
             }
         }
         uint32_t queued = 0u, tqueued = 0u;
@@ -404,7 +405,7 @@ __global__ __launch_bounds__(256, RTW_GPRIMARY_MINB) void gprimary_kernel(const 
             const int i = only_sample >= 0 ? only_sample : (int)((uint32_t)r - po * nsub);
             const int pass = g.first_pass + (int)kpass;
             PathRng rng; rng_init(rng, p.seed, phase, (uint64_t)npix, (uint32_t)pixel, (uint32_t)pass, (uint32_t)i);
-            const Ray ray = camera_ray_xy(p, px, py, i, rng);
+            const Ray ray = camera_ray_xy<CAM>(p, px, py, i, rng);
             if (STATS && live) ct.cams++;
             const uint32_t slot = group_slot(g, b, (uint32_t)lane, (uint32_t)i, kpass);
             f3 si = mk(0, 0, 0);

@@ -56,11 +56,11 @@ void build_tree(HostMesh& m);
 void build_tnodes(HostMesh& m, int top_budget);
 // Flat hierarchy: leaf boxes in preorder and the unions of every 16 / 256 consecutive leaves (needs build_tree()).
 void build_flat(HostMesh& m);
-// Screen-space bins of the reference camera (Src/RayTracerProgram.cpp:133-165: origin (0,0,7), image plane z = -0.5)
+// Screen-space bins of a camera (the reference's own, Src/RayTracerProgram.cpp:133-165, is rtw_default_camera())
 // for a width x height frame cut into bin_w x bin_h pixel bins: for each bin the leaves (node indices, ascending) whose
 // box the line of any camera ray of the bin's pixels can meet.  Returns false (no bins) when some leaf box is not
 // wholly in front of the camera.
-bool build_bins(const HostMesh& m, int width, int height, int bin_w, int bin_h, std::vector<uint32_t>& off, std::vector<uint32_t>& ent);
+bool build_bins(const HostMesh& m, const RtwCamera& camera, int width, int height, int bin_w, int bin_h, std::vector<uint32_t>& off, std::vector<uint32_t>& ent);
 
 // tables
 uint32_t rand31(uint32_t seed, uint32_t pixel, uint32_t sample, uint32_t counter);

@@ -105,6 +105,55 @@ struct RtwSceneDev {
     RtwShapeDev shapes[RTW_DEV_MAX_SHAPES];
 };
 
+// The camera (rtw_camera of rtwin.h): pixel (x, y), sub-sample offset (ox, oy) looks along
+//   v[k] = (right[k] * (dx + ox) + up[k] * (dy + oy)) + forward[k] * focal,   dir = normalized(v),   origin = eye
+// with dx, dy as the reference computes them (Src/RayTracerProgram.cpp:141-142).  The reference's own camera is
+// eye (0, 0, 7), right (1, 0, 0), up (0, 1, 0), forward (0, 0, -1), focal 0.5.
+struct RtwCamera { float eye[3], right[3], up[3], forward[3]; float focal; };
+static_assert(sizeof(RtwCamera) == 52, "RtwCamera");
+inline RtwCamera rtw_default_camera()
+{
+    const RtwCamera c = { { 0.0f, 0.0f, 7.0f }, { 1.0f, 0.0f, 0.0f }, { 0.0f, 1.0f, 0.0f }, { 0.0f, 0.0f, -1.0f }, 0.5f };
+    return c;
+}
+
+// What the screen-bin builders (scene_host.cpp build_bins, rtw_build_kernels.h bins_of_leaf) need of a camera, in double: computed once
+// on the host by bins_camera() and handed to both, so that the two routines start from the same numbers.
+struct RtwBinsCam {
+    double eye[3], right[3], up[3], forward[3];
+    double k;                       // 2 * focal * height: a point q (relative to the eye) is seen at x = W/2 - k (q.right) / (q.forward)
+    double margin;                  // pixels a leaf's projection is grown by (below)
+    float eye_f[3];                 // the eye as the kernels' rays carry it (the facing test is the reference's float test)
+    int32_t ok;                     // 0: this camera gets no bins at all
+};
+// The margin.  (1) Jitter: a sub-sample looks through a point up to 1.25 / (4 W) off its pixel centre in dx and dy
+// (Src/RayTracerProgram.cpp:147-162), i.e. 1.25 H / (2 W) pixels; plus one pixel of slack.  (2) A basis that is orthonormal only to
+// rounding.  With a = dx + ox, b = dy + oy, f = focal a ray's direction is v = a R + b U + f F and a point on it q = t v, so the builders see
+//   q.R = t (a R.R + b U.R + f F.R) = t (a + n),     q.F = t (a R.F + b U.F + f F.F) = t (f + d),     |n|, |d| <= e S
+// where e = the largest of |R.R - 1|, |U.U - 1|, |F.F - 1|, |R.U|, |R.F|, |U.F| and S = A + B + f, A >= |a|, B >= |b| on the screen
+// (A = W / (4 H) + 1.25 / (4 W), B = 1 / 4 + 1.25 / (4 W)).  The projected a' = f (a + n) / (f + d) differs from a by
+//   |a' - a| = |f n - a d| / |f + d| <= e S (f + A) / (f - e S) = e S (1 + A / f) / (1 - e S / f)
+// (the same for b with B; the larger of A and B is used for both), which is 2 H times as much in pixels.  e is measured in double from the
+// struct's floats: exactly 0 for the default camera (whose margin is therefore the fixed camera's), ~1e-7 after rtw_camera_look_at,
+// at most ~3e-4 for a basis the validation accepts.  A camera with e S >= f / 2 gets no bins.
+inline RtwBinsCam rtw_bins_camera(const RtwCamera& c, int width, int height)
+{
+    RtwBinsCam b;
+    for (int k = 0; k < 3; k++) { b.eye[k] = c.eye[k]; b.right[k] = c.right[k]; b.up[k] = c.up[k]; b.forward[k] = c.forward[k]; b.eye_f[k] = c.eye[k]; }
+    const double f = (double)c.focal, W = (double)width, H = (double)height;
+    b.k = 2.0 * f * H;
+    auto dot = [](const double* u, const double* v) { return u[0] * v[0] + u[1] * v[1] + u[2] * v[2]; };
+    auto ab = [](double x) { return x < 0 ? -x : x; };
+    double e = ab(dot(b.right, b.right) - 1.0);
+    const double o[5] = { ab(dot(b.up, b.up) - 1.0), ab(dot(b.forward, b.forward) - 1.0), ab(dot(b.right, b.up)), ab(dot(b.right, b.forward)), ab(dot(b.up, b.forward)) };
+    for (int i = 0; i < 5; i++) if (o[i] > e) e = o[i];
+    const double A = W / (4.0 * H) + 1.25 / (4.0 * W), B = 0.25 + 1.25 / (4.0 * W), M = A > B ? A : B, S = A + B + f;
+    b.ok = (f > 0 && e == e && e * S < 0.5 * f) ? 1 : 0;
+    b.margin = 1.0 + 1.25 * H / (2.0 * W);
+    if (b.ok && e > 0) b.margin += 2.0 * H * (e * S * (1.0 + M / f) / (1.0 - e * S / f));
+    return b;
+}
+
 struct RtwRenderParams {
     int32_t width, height;
     int32_t begin, count;           // linear work items: pixel = map(begin + i)
@@ -123,6 +172,8 @@ struct RtwRenderParams {
     const uint32_t* tile_order;     // full-frame launches: the order in which the primary kernel takes the tiles (null = as numbered)
     const float* cam_dx;            // tiled mapping: dx of every pixel column / dy of every pixel row (Src/RayTracerProgram.cpp:141-142),
     const float* cam_dy;            // computed once on the host with the same float operations
+    RtwCamera cam;                  // the scene's camera, by value (wave-uniform: scalar registers)
+    int32_t cam_general;            // 0: cam is the default camera bit for bit -> the kernels' fixed-pose instantiations (constants instead of cam); 1: the general ones
 };
 
 // screen-space bins of one shape for one (width, height, tile shape): CSR over the bins, entries = node index of a leaf, ascending

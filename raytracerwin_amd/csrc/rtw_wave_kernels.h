@@ -243,6 +243,7 @@ __device__ __forceinline__ void wave_find_intersection(const RtwSceneDev* __rest
 // The jobs [job0, n_jobs) of the job table are tiles whose bins are empty for every shape: each sample sees the sky
 // (Src/RayTracerScene.cpp:89-94).  A kernel of its own, launched beside primary_bins_kernel on a second stream: it needs a
 // fraction of that kernel's registers (no spills of scalar registers into vector lanes) and nothing later in the pass waits for it.
+template <bool CAM>
 __global__ __launch_bounds__(256) void primary_sky_kernel(const float* __restrict__ gamma_thr, float4* __restrict__ accum, uint32_t* __restrict__ argb,
                                                           RtwRenderParams p, int job0)
 {
@@ -264,7 +265,7 @@ __global__ __launch_bounds__(256) void primary_sky_kernel(const float* __restric
         f3 csum = mk(0, 0, 0);
         for (int i = 0; i < p.sub_samples; i++) {
             PathRng rng; rng_init(rng, p.seed, phase, (uint64_t)npix, (uint32_t)pixel, (uint32_t)p.pass_index, (uint32_t)i);
-            const Ray ray = camera_ray_xy(p, px, py, i, rng);
+            const Ray ray = camera_ray_xy<CAM>(p, px, py, i, rng);
             const f3 si = p.max_bounce != 0 ? sky_color(ray.d.y) : mk(0, 0, 0);       // RayTrace(.., 0) is black (Src/RayTracerScene.cpp:39)
             csum = csum + si;
         }
@@ -281,7 +282,7 @@ __global__ __launch_bounds__(256) void primary_sky_kernel(const float* __restric
 }
 
 // ---- primary rays through the screen bins ------------------------------------------------------------------------
-template <bool STATS, bool AN>
+template <bool STATS, bool AN, bool CAM>
 __global__ __launch_bounds__(256) void primary_bins_kernel(const RtwSceneDev* __restrict__ sc, float4* __restrict__ accum,
                                                            uint32_t* __restrict__ argb, PipeBufs pb, RtwRenderParams p)
 {
@@ -334,7 +335,7 @@ __global__ __launch_bounds__(256) void primary_bins_kernel(const RtwSceneDev* __
     for (int i = 0; i < p.sub_samples; i++) {                // wave-uniform loop
         if (only_sample >= 0 && i != only_sample) continue;
         PathRng rng; rng_init(rng, p.seed, phase, (uint64_t)npix, (uint32_t)(live ? pixel : 0), (uint32_t)p.pass_index, (uint32_t)i);
-        const Ray ray = camera_ray_xy(p, px, py, i, rng);
+        const Ray ray = camera_ray_xy<CAM>(p, px, py, i, rng);
         if (STATS && live) ct.cams++;
         f3 si = mk(0, 0, 0);
         bool queue_it = false;

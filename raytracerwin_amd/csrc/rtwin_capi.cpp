@@ -165,11 +165,13 @@ struct rtw_scene {
                                         // (one RayHitResult serves all shapes, Src/RayTracerScene.cpp:99-125) -> single-kernel pipeline
     int prune = 1;
     int traversal = 1;
+    RtwCamera camera = rtw_default_camera();    // rtw_scene_set_camera; travels by value in every launch's parameters
     RtwSceneDev* d_scene = nullptr;
     std::vector<void*> allocs;
+    size_t allocs_at_commit = 0;        // allocs past this mark are the screen bins and tile tables of the current camera
     std::vector<const RtwNode*> d_nodes_of;     // per shape: the device-built tree and leaf records (null: built on the host)
     std::vector<const RtwTri*> d_tris_of;
-    // screen-space bins of the reference camera, one set per (width, height, bin shape) this scene has been rendered at
+    // screen-space bins of the scene's camera, one set per (width, height, bin shape) this scene has been rendered at
     struct JobTable { int task_rows, rank, world, spp; const uint32_t* d_order; int n_jobs, n_busy; };     // n_busy: jobs of tiles with a non-empty bin (they come first)
     // pass-batched pipeline: the launch's tiles split into busy ones (heaviest bins first) and sky-only ones, and the primary kernel's jobs
     struct GroupTable { int task_rows, rank, world, spp; const uint32_t* d_busy; const uint32_t* d_sky; const uint32_t* d_jobs; int n_busy, n_sky, n_jobs; };
@@ -577,6 +579,117 @@ int rtw_scene_set_prune(rtw_scene* scene, int enabled)
     return RTW_OK;
 }
 
+// ---- camera ---------------------------------------------------------------------------------------------------
+namespace {
+inline rtw_camera to_public(const RtwCamera& c) { rtw_camera o; static_assert(sizeof(rtw_camera) == sizeof(RtwCamera), "camera layouts"); std::memcpy(&o, &c, sizeof o); return o; }
+inline RtwCamera to_internal(const rtw_camera& c) { RtwCamera o; std::memcpy(&o, &c, sizeof o); return o; }
+inline bool camera_is_default(const RtwCamera& c) { const RtwCamera d = rtw_default_camera(); return std::memcmp(&c, &d, sizeof c) == 0; }
+const char* camera_problem(const RtwCamera& c)
+{
+    const float* f = c.eye;
+    for (int i = 0; i < 13; i++) if (!std::isfinite(f[i])) return "camera: non-finite value";
+    if (!(c.focal > 0.0f)) return "camera: focal must be positive";
+    const float* ax[3] = { c.right, c.up, c.forward };
+    for (int i = 0; i < 3; i++) {
+        const double len = std::sqrt((double)ax[i][0] * ax[i][0] + (double)ax[i][1] * ax[i][1] + (double)ax[i][2] * ax[i][2]);
+        if (!(std::fabs(len - 1.0) <= 1e-4)) return "camera: right, up and forward must be unit vectors (to within 1e-4)";
+        const float* o = ax[(i + 1) % 3];
+        const double d = (double)ax[i][0] * o[0] + (double)ax[i][1] * o[1] + (double)ax[i][2] * o[2];
+        if (!(std::fabs(d) <= 1e-4)) return "camera: right, up and forward must be mutually orthogonal (to within 1e-4)";
+    }
+    return nullptr;
+}
+// RMath::Random of the path's stream (rtw_device.hip PathRng::random)
+inline float camera_uniform(uint32_t seed, uint32_t pixel, uint32_t sample, uint32_t counter) { return (float)(int32_t)rtw::rand31(seed, pixel, sample, counter) / 2147483648.0f; }
+}  // namespace
+
+int rtw_camera_default(rtw_camera* out)
+{
+    if (!out) return fail(RTW_ERR_INVALID, "out is null");
+    *out = to_public(rtw_default_camera());
+    return RTW_OK;
+}
+
+int rtw_camera_look_at(const float eye[3], const float target[3], const float up_hint[3], float vfov_degrees, rtw_camera* out)
+{
+    if (!eye || !target || !up_hint || !out) return fail(RTW_ERR_INVALID, "null argument");
+    for (int k = 0; k < 3; k++) if (!std::isfinite(eye[k]) || !std::isfinite(target[k]) || !std::isfinite(up_hint[k])) return fail(RTW_ERR_INVALID, "look_at: non-finite value");
+    if (!std::isfinite(vfov_degrees) || !(vfov_degrees > 0.0f) || !(vfov_degrees < 180.0f)) return fail(RTW_ERR_INVALID, "look_at: vfov must lie inside (0, 180) degrees");
+    // the basis in double, rounded to float once (a -0 becomes +0: the default pose then comes out as the default struct, bit for bit)
+    auto norm3 = [](double v[3]) { const double l = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); if (!(l > 0)) return false; for (int k = 0; k < 3; k++) v[k] /= l; return true; };
+    double f[3] = { (double)target[0] - eye[0], (double)target[1] - eye[1], (double)target[2] - eye[2] };
+    if (!norm3(f)) return fail(RTW_ERR_INVALID, "look_at: target equals eye");
+    double h[3] = { up_hint[0], up_hint[1], up_hint[2] };
+    if (!norm3(h)) return fail(RTW_ERR_INVALID, "look_at: up_hint is zero");
+    double r[3] = { f[1] * h[2] - f[2] * h[1], f[2] * h[0] - f[0] * h[2], f[0] * h[1] - f[1] * h[0] };
+    if (!(std::sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]) > 1e-6) || !norm3(r)) return fail(RTW_ERR_INVALID, "look_at: up_hint is parallel to the viewing direction");
+    const double u[3] = { r[1] * f[2] - r[2] * f[1], r[2] * f[0] - r[0] * f[2], r[0] * f[1] - r[1] * f[0] };
+    RtwCamera c;
+    for (int k = 0; k < 3; k++) { c.eye[k] = eye[k]; c.right[k] = (float)(r[k] + 0.0); c.up[k] = (float)(u[k] + 0.0); c.forward[k] = (float)(f[k] + 0.0); }
+    // 0.25 / tan(vfov / 2): the tangent in double, rounded to float, one float divide (2 atan(0.5) in degrees, as a float, gives exactly 0.5)
+    c.focal = 0.25f / (float)std::tan((double)vfov_degrees * (3.14159265358979323846 / 360.0));
+    if (const char* why = camera_problem(c)) return fail(RTW_ERR_INVALID, why);
+    *out = to_public(c);
+    return RTW_OK;
+}
+
+static int drop_camera_tables(rtw_scene* scene);
+int rtw_scene_set_camera(rtw_scene* scene, const rtw_camera* cam)
+{
+    if (!scene) return fail(RTW_ERR_INVALID, "scene is null");
+    const RtwCamera c = cam ? to_internal(*cam) : rtw_default_camera();
+    if (const char* why = camera_problem(c)) return fail(RTW_ERR_INVALID, why);
+    if (std::memcmp(&c, &scene->camera, sizeof c) == 0) return RTW_OK;
+    if (scene->committed && scene->ctx) { const int rc = drop_camera_tables(scene); if (rc != RTW_OK) return rc; }
+    scene->camera = c;
+    return RTW_OK;
+}
+
+int rtw_scene_get_camera(const rtw_scene* scene, rtw_camera* out)
+{
+    if (!scene || !out) return fail(RTW_ERR_INVALID, "null argument");
+    *out = to_public(scene->camera);
+    return RTW_OK;
+}
+
+int rtw_camera_rays(const rtw_camera* cam, int width, int height, const int32_t* pixels, int64_t n, int pass_index, int sub_sample, uint32_t seed, float* rays7)
+{
+    if (width <= 0 || height <= 0 || n < 0 || (n > 0 && (!pixels || !rays7))) return fail(RTW_ERR_INVALID, "bad argument");
+    if (pass_index < 0 || sub_sample < 0 || sub_sample > 3) return fail(RTW_ERR_INVALID, "pass_index >= 0 and sub_sample in 0..3");
+    if ((int64_t)width * height > INT32_MAX) return fail(RTW_ERR_LIMIT, "frame too large");
+    const RtwCamera c = cam ? to_internal(*cam) : rtw_default_camera();
+    if (const char* why = camera_problem(c)) return fail(RTW_ERR_INVALID, why);
+    const float aspect = (float)width / (float)height;
+    const float inv_pixel_radius = 1.0f / (width * 4);
+    const float offset_radius = inv_pixel_radius * 0.5f;
+    for (int64_t j = 0; j < n; j++) {
+        const int pixel = pixels[j];
+        if (pixel < 0 || pixel >= width * height) return fail(RTW_ERR_INVALID, "pixel outside the frame");
+        // ThreadWorker_Render's ray (Src/RayTracerProgram.cpp:141-165) as rtw_device.hip camera_ray builds it
+        const int x = pixel % width, y = pixel / width;
+        const float dx = -(float)(x - width / 2) / (width * 2) * aspect;
+        const float dy = -(float)(y - height / 2) / (height * 2);
+        float ox = (sub_sample & 1) ? inv_pixel_radius : 0.0f;
+        float oy = (sub_sample & 2) ? inv_pixel_radius : 0.0f;
+        const uint32_t sample = (uint32_t)pass_index * 4u + (uint32_t)sub_sample;
+        ox += (camera_uniform(seed, (uint32_t)pixel, sample, 0u) - 0.5f) * offset_radius;
+        oy += (camera_uniform(seed, (uint32_t)pixel, sample, 1u) - 0.5f) * offset_radius;
+        const float a = dx + ox, b = dy + oy;
+        float v[3];
+        for (int k = 0; k < 3; k++) {
+            const float ra = c.right[k] * a, ub = c.up[k] * b, ff = c.forward[k] * c.focal;
+            const float s = ra + ub;
+            v[k] = s + ff;
+        }
+        const float xx = v[0] * v[0], yy = v[1] * v[1], zz = v[2] * v[2];
+        const float sq0 = xx + yy; const float sq = sq0 + zz;
+        if (!(std::fabs(sq) < FLT_EPSILON)) { const float inv = 1.0f / sqrtf(sq); v[0] *= inv; v[1] *= inv; v[2] *= inv; }
+        float* r = rays7 + (size_t)j * 7;
+        r[0] = c.eye[0]; r[1] = c.eye[1]; r[2] = c.eye[2]; r[3] = v[0]; r[4] = v[1]; r[5] = v[2]; r[6] = 1000.0f;
+    }
+    return RTW_OK;
+}
+
 static double commit_now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 #define COMMIT_MARK(what) do { if (trace) { (void)hipStreamSynchronize(scene->ctx->stream); const double t_ = commit_now(); std::fprintf(stderr, "  commit: %-28s %.3f ms\n", what, t_ - t_last); t_last = t_; } } while (0)
 int rtw_scene_commit(rtw_scene* scene)
@@ -697,7 +810,23 @@ int rtw_scene_commit(rtw_scene* scene)
     scene->allocs.push_back(dsc);
     HIP_TRY(hipMemcpy(dsc, h.get(), sizeof(RtwSceneDev), hipMemcpyHostToDevice));
     scene->d_scene = (RtwSceneDev*)dsc;
+    scene->allocs_at_commit = scene->allocs.size();
     scene->committed = true;
+    return RTW_OK;
+}
+
+// A committed scene gets another camera: nothing in flight may still read the old pose's bins and tile tables, which are then freed
+// (the next render call builds the new pose's).
+static int drop_camera_tables(rtw_scene* scene)
+{
+    rtw_context* cx = scene->ctx;
+    HIP_TRY(hipSetDevice(cx->device));
+    HIP_TRY(hipStreamSynchronize(cx->stream));
+    if (cx->aux_stream) HIP_TRY(hipStreamSynchronize(cx->aux_stream));
+    for (int j = 1; j < RTW_MAX_PARTS; j++) if (cx->part_stream[j]) HIP_TRY(hipStreamSynchronize(cx->part_stream[j]));
+    for (size_t i = scene->allocs_at_commit; i < scene->allocs.size(); i++) (void)hipFree(scene->allocs[i]);
+    scene->allocs.resize(scene->allocs_at_commit);
+    scene->bin_sets.clear();
     return RTW_OK;
 }
 
@@ -758,7 +887,7 @@ int rtw_scene_mesh_bins(const rtw_scene* scene, int shape, int width, int height
         off.resize(n_bins + 1);
         uint32_t *d_off = nullptr, *d_ent = nullptr; int has = 0;
         const hipError_t be = (hipError_t)rtw::device_build_bins(scene->d_nodes_of[(size_t)shape], scene->d_tris_of[(size_t)shape], (int)scene->meshes[(size_t)shape]->nodes.size(),
-                                                                 width, height, bin_w, bin_h, &d_off, &d_ent, off.data(), &has, scene->ctx->stream);
+                                                                 scene->camera, width, height, bin_w, bin_h, &d_off, &d_ent, off.data(), &has, scene->ctx->stream);
         if (be != hipSuccess) return hip_fail(be, "device bins build");
         ok = has != 0;
         if (ok) {
@@ -768,7 +897,7 @@ int rtw_scene_mesh_bins(const rtw_scene* scene, int shape, int width, int height
             if (ce != hipSuccess) return hip_fail(ce, "bins read-back");
         }
     } else {
-        ok = rtw::build_bins(*scene->meshes[(size_t)shape], width, height, bin_w, bin_h, off, ent);
+        ok = rtw::build_bins(*scene->meshes[(size_t)shape], scene->camera, width, height, bin_w, bin_h, off, ent);
     }
     counts2[0] = ok ? (int64_t)off.size() : 0; counts2[1] = ok ? (int64_t)off.back() : 0;
     if (!ok) return 0;                   // this mesh gets no bins (not wholly in front of the camera, or the frame does not tile)
@@ -954,7 +1083,7 @@ static int scene_bins(rtw_scene* scene, int width, int height, int bin_w, int bi
             // the same lists from the device: counted, scanned, filled and sorted there (rtw_build_kernels.h); only the offsets come back (tile weights)
             off.resize(n_bins + 1);
             uint32_t *d_off = nullptr, *d_ent = nullptr; int has = 0;
-            const hipError_t be = (hipError_t)rtw::device_build_bins(scene->d_nodes_of[s], scene->d_tris_of[s], (int)scene->meshes[s]->nodes.size(), width, height, bin_w, bin_h,
+            const hipError_t be = (hipError_t)rtw::device_build_bins(scene->d_nodes_of[s], scene->d_tris_of[s], (int)scene->meshes[s]->nodes.size(), scene->camera, width, height, bin_w, bin_h,
                                                                      &d_off, &d_ent, off.data(), &has, scene->ctx->stream);
             if (be != hipSuccess) return hip_fail(be, "device bins build");
             if (!has) { for (auto& w : weight) w += 1000u; continue; }
@@ -963,7 +1092,7 @@ static int scene_bins(rtw_scene* scene, int width, int height, int bin_w, int bi
             h[s].off = d_off; h[s].ent = d_ent;
             continue;
         }
-        if (!rtw::build_bins(*scene->meshes[s], width, height, bin_w, bin_h, off, ent)) { for (auto& w : weight) w += 1000u; continue; }
+        if (!rtw::build_bins(*scene->meshes[s], scene->camera, width, height, bin_w, bin_h, off, ent)) { for (auto& w : weight) w += 1000u; continue; }
         for (size_t b = 0; b < n_bins; b++) weight[b] += off[b + 1] - off[b];
         int rc;
         if ((rc = upload(scene, off, &h[s].off)) != RTW_OK) return rc;
@@ -1242,6 +1371,7 @@ static int render_group(rtw_scene* scene, rtw_framebuffer* fb, RtwRenderParams p
     rtw_context* cx = scene->ctx;
     p.width = fb->width; p.height = fb->height;
     p.max_bounce = max_bounce; p.preview = use_base_color ? 1 : 0; p.pass_index = first_pass; p.sub_samples = sub_samples; p.seed = seed;
+    p.cam = scene->camera; p.cam_general = camera_is_default(scene->camera) ? 0 : 1;
     if (!choose_group_tiles(p, range_begin, range_end)) return fail(RTW_ERR_LIMIT, "frame too large for the tile mapping");
     rtw_scene::BinSet* bs = nullptr;
     int rc = scene_bins(scene, p.width, p.height, p.tile_w, p.tile_h, &bs); if (rc != RTW_OK) return rc;
@@ -1365,6 +1495,7 @@ static int render_common(rtw_scene* scene, rtw_framebuffer* fb, RtwRenderParams&
     int rc = check_render_args(scene, fb, max_bounce, pass_index, sub_samples); if (rc != RTW_OK) return rc;
     p.width = fb->width; p.height = fb->height;
     p.max_bounce = max_bounce; p.preview = use_base_color ? 1 : 0; p.pass_index = pass_index; p.sub_samples = sub_samples; p.seed = seed;
+    p.cam = scene->camera; p.cam_general = camera_is_default(scene->camera) ? 0 : 1;
     rtw_context* cx = scene->ctx;
     hipError_t e;
     // the bins + wave pipeline needs whole rows, the flat hierarchy (traversal != 0) and a frame that tiles; a scene whose analytic hits can inherit a texel

@@ -418,39 +418,48 @@ void build_flat(HostMesh& m)
 }
 
 // ---------------------------------------------------------------------------------------
-// Screen-space bins of the reference's fixed camera.  Pixel (x, y), sub-sample offset (ox, oy) looks along
-// (dx + ox, dy + oy, -0.5) with dx = -(x - W/2) / (2W) * (W/H), dy = -(y - H/2) / (2H) (Src/RayTracerProgram.cpp:141-165),
-// so a point q (relative to the camera, q.z < 0) is seen at x = W/2 + H q.x / q.z, y = H/2 + H q.y / q.z (the offsets
-// move a sample by less than half a pixel).  A bin lists the leaves whose triangle a camera ray of the bin's pixels could
+// Screen-space bins of the scene's camera.  Pixel (x, y), sub-sample offset (ox, oy) looks along
+// (dx + ox) right + (dy + oy) up + focal forward with dx = -(x - W/2) / (2W) * (W/H), dy = -(y - H/2) / (2H) (Src/RayTracerProgram.cpp:141-165),
+// so a point q (relative to the eye, depth = q.forward > 0) is seen at x = W/2 - 2 focal H (q.right) / depth, y = H/2 - 2 focal H (q.up) / depth
+// (the offsets move a sample by less than half a pixel).  For the reference's own camera -- eye (0, 0, 7), the axes, focal 0.5 -- these are
+// x = W/2 + H q.x / q.z, y = H/2 + H q.y / q.z with the same roundings.  A bin lists the leaves whose triangle a camera ray of the bin's pixels could
 // ACCEPT: the triangle faces the camera (the reference's own float test, identical for every camera ray) and its projection,
 // grown by a one-pixel margin, touches the bin (separating-axis test against the bin's rectangle).  A leaf left out would have
 // been box- or triangle-tested by the reference and rejected, which changes no result; the kernel still runs the reference's
 // box and triangle tests on every listed leaf, per ray.
 // ---------------------------------------------------------------------------------------
-bool build_bins(const HostMesh& m, int width, int height, int bin_w, int bin_h, std::vector<uint32_t>& off, std::vector<uint32_t>& ent)
+bool build_bins(const HostMesh& m, const RtwCamera& camera, int width, int height, int bin_w, int bin_h, std::vector<uint32_t>& off, std::vector<uint32_t>& ent)
 {
     off.clear(); ent.clear();
     if (width <= 0 || height <= 0 || bin_w <= 0 || bin_h <= 0) return false;
+    const RtwBinsCam cam = rtw_bins_camera(camera, width, height);
+    if (!cam.ok) return false;
     const int bx = (width + bin_w - 1) / bin_w, by = (height + bin_h - 1) / bin_h;      // the bins at the right / bottom edge may be partial
-    const double cx = (double)(width / 2), cy = (double)(height / 2), H = (double)height;
+    const double cx = (double)(width / 2), cy = (double)(height / 2);
     // A sub-sample looks through a point up to 1.25 / (4 W) off its pixel centre in dx and dy (Src/RayTracerProgram.cpp:147-162), i.e.
     // 1.25 H / (2 W) PIXELS (a pixel is 1 / (2 H) wide in those units): under half a pixel for landscape frames, several pixels for tall
-    // narrow ones.  The margin covers that plus a pixel of slack.
-    const double margin = 1.0 + 1.25 * (double)height / (2.0 * (double)width);
+    // narrow ones.  The margin covers that plus a pixel of slack, plus what a basis that is orthonormal only to rounding can move a
+    // projection by (rtw_types.h rtw_bins_camera: nothing for the default camera).
+    const double margin = cam.margin;
     struct Item { int node, bin; };
     std::vector<Item> items;
     items.reserve(m.tris.size() * 4);
     for (size_t i = 0; i < m.nodes.size(); i++) {
         const RtwNode& nd = m.nodes[i];
         if (nd.tri < 0) continue;
-        const double zmax = (double)nd.max_z - 7.0;
-        if (!(zmax < -0.01)) return false;                      // not wholly in front of the camera: no bins for this mesh
+        // all eight corners of the leaf's box in front of the eye (depth = q . forward > 0.01), else no bins for this mesh
+        for (int c = 0; c < 8; c++) {
+            const double qx = (double)((c & 1) ? nd.max_x : nd.min_x) - cam.eye[0], qy = (double)((c & 2) ? nd.max_y : nd.min_y) - cam.eye[1],
+                         qz = (double)((c & 4) ? nd.max_z : nd.min_z) - cam.eye[2];
+            const double depth = qx * cam.forward[0] + qy * cam.forward[1] + qz * cam.forward[2];
+            if (!(depth > 0.01)) return false;
+        }
         const RtwTri& t = m.tris[(size_t)nd.tri];
-        // Every camera ray starts at (0, 0, 7): the reference's first rejection, "origin behind the triangle's plane"
+        // Every camera ray starts at the eye: the reference's first rejection, "origin behind the triangle's plane"
         // (d2 = N.O - N.P0 < 0, Src/RRay.cpp:156-160), is the same float computation for all of them, so a triangle that
         // fails it is accepted by no camera ray and needs no bin at all.
         {
-            const float ox = 0.0f, oy = 0.0f, oz = 7.0f;
+            const float ox = cam.eye_f[0], oy = cam.eye_f[1], oz = cam.eye_f[2];
             const float d0 = t.nx * ox + t.ny * oy + t.nz * oz;
             const float d2 = d0 - t.d1;
             if (d2 < 0) continue;
@@ -460,8 +469,10 @@ bool build_bins(const HostMesh& m, int width, int height, int bin_w, int bin_h, 
         double sx[3], sy[3];
         bool finite = true;
         for (int k = 0; k < 3; k++) {
-            const double qz = vz[k] - 7.0;
-            sx[k] = cx + H * vx[k] / qz; sy[k] = cy + H * vy[k] / qz;
+            const double qx = vx[k] - cam.eye[0], qy = vy[k] - cam.eye[1], qz = vz[k] - cam.eye[2];
+            const double depth = qx * cam.forward[0] + qy * cam.forward[1] + qz * cam.forward[2];
+            const double qr = qx * cam.right[0] + qy * cam.right[1] + qz * cam.right[2], qu = qx * cam.up[0] + qy * cam.up[1] + qz * cam.up[2];
+            sx[k] = cx - cam.k * qr / depth; sy[k] = cy - cam.k * qu / depth;
             finite = finite && sx[k] == sx[k] && sy[k] == sy[k] && std::fabs(sx[k]) < 1e12 && std::fabs(sy[k]) < 1e12;
         }
         if (!finite) return false;
