@@ -257,6 +257,19 @@ public:
         }
         return shape;
     }
+    // FindIntersectionWithScene for n rays in DEVICE memory (n x 7 floats) into the caller's device buffers (n x 11 floats, n int32, n int32; any of
+    // them may be null, not all), asynchronous on the device's stream: rtw_trace_closest_device
+    void FindIntersectionsDevice(const void* rays, int64_t n, void* hits11, void* shape, void* tri)
+    {
+        Commit();
+        RtwCheck(rtw_trace_closest_device(Scene, rays, n, hits11, shape, tri));
+    }
+    // any-hit: occluded[i] = 1 when ray i hits anything within its distance, else 0 (n bytes of device memory): rtw_trace_occluded_device
+    void OccludedDevice(const void* rays, int64_t n, void* occluded)
+    {
+        Commit();
+        RtwCheck(rtw_trace_occluded_device(Scene, rays, n, occluded));
+    }
     // radiance along one ray (Src/RayTracerScene.cpp:31-97); (pixel, sample) select the random stream
     RVec3 RayTrace(const RRay& InRay, int MaxBounceTimes, const RenderOption& InOption, uint32_t pixel, uint32_t sample, uint32_t seed, int width, int height)
     {

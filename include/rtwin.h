@@ -98,7 +98,13 @@ int rtw_context_synchronize(rtw_context* ctx);
  *                   walked once for up to four rays per lane (sub-samples x passes <= 4); "sky_blocks" (4) blocks of the sky kernel per CU at most;
  *   "workspace_limit_mb" (0 = 24 GiB) a group's workspace may not exceed this: larger groups are re-formed smaller (see rtw_context_memory_bytes);
  *   "device_build" (1) tree, layouts and screen bins built on the device; "hint_period" (16) pipeline 3: the queue lengths that size the next launches
- *                   are read back every n-th pass; "kernel_timing" 1 = record events around the stages of each pass / group (rtw_last_pass_kernel_ms). */
+ *                   are read back every n-th pass; "kernel_timing" 1 = record events around the stages of each pass / group (rtw_last_pass_kernel_ms);
+ *   "query_kernel"  (-1) which kernel the device queries (rtw_trace_closest_device / rtw_trace_occluded_device / rtw_trace_occluded) run: 1 = the ray-per-lane
+ *                   query kernel (rtw_query_kernels.h); 0 = the kernel of rtw_trace_closest on the caller's buffers (any-hit: a closest query whose
+ *                   shape >= 0 becomes the byte) -- the A/B baseline and cross-check; -1 = the measured rule (profiles/query_experiments.md): any-hit on
+ *                   one-mesh scenes runs the query kernel, everything else the old one.  Results never depend on it, nor on the next;
+ *   "query_blocks"  (0 = one grid sized from the device's compute units) > 0: at most exactly that many blocks, so that few rays make many trips of
+ *                   the query kernel's batch loop. */
 int rtw_context_set_option(rtw_context* ctx, const char* name, int value);
 /* with option "kernel_timing" = 1: HIP-event durations (ms) of the latest pass's three stages -- primary kernel(s),
  * the per-bounce trace / shade launches, resolve -- measured on the context's stream; waits for that pass. */
@@ -201,6 +207,23 @@ int rtw_scene_mesh_bins(const rtw_scene* scene, int shape, int width, int height
  * and original triangle index.  Host buffers. */
 int rtw_trace_closest(rtw_scene* scene, const float* rays, int64_t n,
                       float* hits11, int32_t* shape, int32_t* tri);
+/* ---- ray queries on device buffers: closest-hit and any-hit, asynchronous on the context's stream ---- */
+/* FindIntersectionWithScene for n rays that already live in device memory.  rays_dev: n x 7 floats (origin, direction, distance),
+ * hits11_dev: n x 11 floats, shape_dev / tri_dev: n int32 -- the layouts of rtw_trace_closest, byte for byte the values it returns
+ * (misses included).  Any output may be NULL (not stored); at least one must not be.  Asynchronous on the context's stream:
+ * no allocation, no copy, no synchronisation.  The pointers are the caller's (as for rtw_framebuffer_wrap): 4-byte aligned, dense,
+ * inputs and outputs not overlapping.  At most 2^31 - 1 rays per call (RTW_ERR_LIMIT above).
+ * Where the old kernel runs ("query_kernel" 0, or -1 and the rule picks it) and an output is NULL -- or for any-hit -- the old kernel's outputs
+ * go to a stand-in buffer of the context: the first such call, and one with more rays than any before, waits for the stream and allocates. */
+int rtw_trace_closest_device(rtw_scene* scene, const void* rays_dev, int64_t n, void* hits11_dev, void* shape_dev, void* tri_dev);
+/* occluded_dev: n bytes, 1 when rtw_trace_closest would report shape >= 0 for the ray, else 0.  The geometric test only: a texel's alpha
+ * plays no part (it does not in FindIntersectionWithScene either).  A lane stops at its first accepted hit. */
+int rtw_trace_occluded_device(rtw_scene* scene, const void* rays_dev, int64_t n, void* occluded_dev);
+/* the same from / to host arrays (stages through device memory and waits, like rtw_trace_closest) */
+int rtw_trace_occluded(rtw_scene* scene, const float* rays, int64_t n, uint8_t* occluded);
+/* DIAGNOSTIC (tests size a batch larger than one grid sweep with it): threads per block (out2[0]) and blocks (out2[1]) the device queries above launch for n rays with the context's current options
+ * (any_hit: 0 = closest, 1 = occluded); where the old kernel runs: 256 and ceil(n / 256) */
+int rtw_query_launch_shape(rtw_scene* scene, int64_t n, int any_hit, int32_t out2[2]);
 /* RayTracerScene::RayTrace (Src/RayTracerScene.cpp:31-97) for n explicit rays; keys2 holds
  * (pixel, sample) per ray, which select the random stream.  rgb: 3 floats each. */
 int rtw_ray_trace(rtw_scene* scene, const float* rays, const uint32_t* keys2, int64_t n,

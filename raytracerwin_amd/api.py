@@ -572,6 +572,84 @@ class RayTracerScene:
         _check(library().rtw_trace_closest(self.h, _p(rays), C.c_int64(n), _p(hits), _p(shape), _p(tri)))
         return hits, shape, tri
 
+    # ---- ray queries on device buffers (torch tensors): asynchronous on the context's stream.  The caller either gives the context torch's stream
+    # (Context(stream=torch.cuda.current_stream().cuda_stream) / set_stream) or synchronises both sides itself. ----
+    def _query_rays(self, rays, what):
+        """Validation of a torch ray tensor, before any library call: ValueError"""
+        import torch
+        if not isinstance(rays, torch.Tensor):
+            raise ValueError("%s: rays must be a torch tensor on the context's device" % what)
+        if rays.dtype != torch.float32:
+            raise ValueError("%s: rays must be float32, not %s" % (what, rays.dtype))
+        if rays.dim() < 1 or rays.shape[-1] != 7:
+            raise ValueError("%s: the last dimension of rays must be 7 (origin, direction, distance)" % what)
+        if not rays.is_contiguous():
+            raise ValueError("%s: rays must be contiguous" % what)
+        if not rays.is_cuda:
+            raise ValueError("%s: rays live on the CPU; pass a tensor on the context's device" % what)
+        dev = self.ctx.device if self.ctx is not None else 0
+        if rays.device.index != dev:
+            raise ValueError("%s: rays live on %s, the context on device %d" % (what, rays.device, dev))
+        return rays.numel() // 7
+
+    def _query_out(self, want, n, cols, dtype, rays, what):
+        import torch
+        if want is False or want is None:
+            return None
+        if want is True:
+            return torch.empty((n, cols) if cols else (n,), dtype=dtype, device=rays.device)
+        if (not isinstance(want, torch.Tensor) or want.dtype != dtype or not want.is_contiguous() or want.device != rays.device or
+                want.numel() != n * (cols or 1)):
+            raise ValueError("%s: an output tensor must be contiguous %s with %d elements on %s" % (what, dtype, n * (cols or 1), rays.device))
+        return want
+
+    def trace_closest(self, rays, hits=True, shape=True, tri=True):
+        """FindIntersectionWithScene for a torch tensor of rays (n, 7) float32 on the context's device ->
+        (hits (n, 11) float32, shape (n,) int32, tri (n,) int32) on the same device, None for an output switched off
+        (False); an output may also be a tensor to write into.  Byte for byte what FindIntersectionWithScene(numpy) returns."""
+        import torch
+        n = self._query_rays(rays, "trace_closest")
+        outs = (self._query_out(hits, n, 11, torch.float32, rays, "trace_closest"), self._query_out(shape, n, 0, torch.int32, rays, "trace_closest"),
+                self._query_out(tri, n, 0, torch.int32, rays, "trace_closest"))
+        if all(o is None for o in outs):
+            raise ValueError("trace_closest: every output is switched off")
+        self.commit()
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        if n:
+            _check(library().rtw_trace_closest_device(self.h, C.c_void_p(rays.data_ptr()), C.c_int64(n), ptr(outs[0]), ptr(outs[1]), ptr(outs[2])))
+        return outs
+
+    def trace_occluded(self, rays, out=None):
+        """Any-hit: 1 where FindIntersectionWithScene would report a hit, else 0.  A torch tensor (n, 7) on the context's device ->
+        an (n,) uint8 tensor there (asynchronous on the context's stream); a NumPy array goes through the host entry and returns NumPy."""
+        if isinstance(rays, np.ndarray):
+            if rays.dtype != np.float32:
+                raise ValueError("trace_occluded: rays must be float32, not %s" % rays.dtype)
+            if rays.ndim < 1 or rays.shape[-1] != 7:
+                raise ValueError("trace_occluded: the last dimension of rays must be 7 (origin, direction, distance)")
+            if not rays.flags["C_CONTIGUOUS"]:
+                raise ValueError("trace_occluded: rays must be contiguous")
+            n = rays.size // 7
+            occ = np.zeros(n, np.uint8)
+            self.commit()
+            if n:
+                _check(library().rtw_trace_occluded(self.h, _p(rays), C.c_int64(n), _p(occ)))
+            return occ
+        import torch
+        n = self._query_rays(rays, "trace_occluded")
+        occ = self._query_out(True if out is None else out, n, 0, torch.uint8, rays, "trace_occluded")
+        self.commit()
+        if n:
+            _check(library().rtw_trace_occluded_device(self.h, C.c_void_p(rays.data_ptr()), C.c_int64(n), C.c_void_p(occ.data_ptr())))
+        return occ
+
+    def query_launch_shape(self, n, any_hit=False):
+        """(threads per block, blocks) a device query of n rays launches with the context's current options"""
+        self.commit()
+        out = np.zeros(2, np.int32)
+        _check(library().rtw_query_launch_shape(self.h, C.c_int64(int(n)), int(bool(any_hit)), _p(out)))
+        return int(out[0]), int(out[1])
+
     def RayTrace(self, rays, keys, MaxBounceTimes, InOption=None, seed=12345, width=1920, height=1080):
         self.commit()
         opt = InOption or RenderOption()

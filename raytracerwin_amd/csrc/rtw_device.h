@@ -90,6 +90,18 @@ int device_build_bins(const RtwNode* d_nodes, const RtwTri* d_tris, int n_nodes,
 #define RTW_TNODES_TOP_BUDGET 3072 // records (32 B each) of a tree's upper levels a block of the ray-per-lane trace kernel stages in LDS: 96 KiB
 int launch_render(const RtwSceneDev* sc, void* accum, void* argb, void* ws, const RtwRenderParams& p, bool stats, hipStream_t stream);
 int launch_closest(const RtwSceneDev* sc, const float* rays, long long n, float* hits11, int* shape, int* tri, bool stats, hipStream_t stream);
+// ---- ray queries on the caller's device buffers (rtw_query_kernels.h) ----
+struct QueryTuning {
+    int cu_count = 256;
+    int blocks = 0;                          // > 0: at most exactly this many blocks (option "query_blocks"); 0: cu_count x blocks per CU
+    bool single_mesh = false;                // the scene is one mesh: the instantiation without the analytic tests
+    bool carry = false;                      // an analytic shape follows a textured mesh: its hits can keep that mesh hit's sampled colour
+    int staged_shape = -1, staged_top = 0;   // as GroupTuning: the first mesh whose upper tree levels a block stages in LDS
+    bool staged_all = false;
+};
+void query_launch_shape(const QueryTuning& q, long long n, int* threads, unsigned* blocks);
+int launch_shape_to_byte(const int* shape, long long n, uint8_t* out, hipStream_t stream);       // out[i] = shape[i] >= 0
+int launch_query(const RtwSceneDev* sc, const float* rays, long long n, float* hits11, int* shape, int* tri, uint8_t* occluded, const QueryTuning& q, bool stats, hipStream_t stream);
 int launch_ray_trace(const RtwSceneDev* sc, const float* rays, const uint32_t* keys2, long long n, int max_bounce, int preview,
                      uint32_t seed, unsigned long long npix, float* rgb, void* ws, bool stats, hipStream_t stream);
 int launch_texture_sample(const RtwSceneDev* sc, int shape, int mat, const float* uv, long long n, float* rgba, hipStream_t stream);

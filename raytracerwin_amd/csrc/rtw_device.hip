@@ -1112,6 +1112,7 @@ __global__ __launch_bounds__(256, 3) void shade_kernel(const RtwSceneDev* __rest
 
 #include "rtw_wave_kernels.h"
 #include "rtw_group_kernels.h"
+#include "rtw_query_kernels.h"
 #include "rtw_build_kernels.h"
 
 __global__ __launch_bounds__(256) void resolve_kernel(const RtwSceneDev* __restrict__ sc, float4* __restrict__ accum,
@@ -1164,6 +1165,13 @@ __global__ __launch_bounds__(256) void closest_kernel(const RtwSceneDev* __restr
     o[7] = h.color.x; o[8] = h.color.y; o[9] = h.color.z; o[10] = h.alpha;
     shape[i] = s; tri[i] = s >= 0 ? t : -1;
     if (STATS) flush_counters(sc, ct);
+}
+
+// rtw_trace_occluded_device under "query_kernel" 0: the closest query's shape as the byte
+__global__ __launch_bounds__(256) void shape_to_byte_kernel(const int* __restrict__ shape, long long n, uint8_t* __restrict__ out)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = shape[i] >= 0 ? (uint8_t)1 : (uint8_t)0;
 }
 
 template <bool STATS>
@@ -1759,6 +1767,61 @@ int launch_closest(const RtwSceneDev* sc, const float* rays, long long n, float*
     const unsigned grid = (unsigned)((n + block - 1) / block);
     if (stats) hipLaunchKernelGGL(closest_kernel<true>, dim3(grid), dim3(block), 0, stream, sc, rays, n, hits11, shape, tri);
     else hipLaunchKernelGGL(closest_kernel<false>, dim3(grid), dim3(block), 0, stream, sc, rays, n, hits11, shape, tri);
+    return (int)hipGetLastError();
+}
+
+int launch_shape_to_byte(const int* shape, long long n, uint8_t* out, hipStream_t stream)
+{
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(shape_to_byte_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, shape, n, out);
+    return (int)hipGetLastError();
+}
+
+// threads per block and blocks of a query launch: 1024-thread blocks (one per CU: they share the staged tree) when a tree's upper levels are staged,
+// 256-thread blocks otherwise; never more blocks than there are rays for.  (512-thread blocks for the closest query -- 256 registers a lane, no
+// spill beyond the walk's own -- were measured 6 to 37 % slower than the 1024-thread ones: profiles/query_experiments.md)
+void query_launch_shape(const QueryTuning& q, long long n, int* threads, unsigned* blocks)
+{
+    const bool staged = q.staged_shape >= 0 && q.staged_top > 0;
+    const int nt = staged ? 1024 : 256;
+    long long most = q.blocks > 0 ? (long long)q.blocks : (long long)q.cu_count * (staged ? 1 : 8);
+    const long long need = (n + nt - 1) / nt;
+    if (most > need) most = need;
+    if (most < 1) most = 1;
+    *threads = nt; *blocks = (unsigned)most;
+}
+
+// occluded != null: the any-hit query (the other outputs are not looked at); else the closest-hit query, null outputs are not stored
+int launch_query(const RtwSceneDev* sc, const float* rays, long long n, float* hits11, int* shape, int* tri, uint8_t* occluded, const QueryTuning& q, bool stats, hipStream_t stream)
+{
+    if (n <= 0) return 0;
+    int nt; unsigned blocks;
+    const bool any = occluded != nullptr, an = !q.single_mesh;
+    query_launch_shape(q, n, &nt, &blocks);
+    const int carry = q.carry ? 1 : 0;
+#define RTW_LAUNCH_Q(ST, AN_, NT_, CAP_, STG, ANY_, DYN)                                                                                          \
+    do {                                                                                                                                        \
+        static bool lds_raised = false;      /* once per instantiation, to the most any scene can ask for (candidate lists + RTW_TNODES_TOP_BUDGET records) */ \
+        if (STG != 0 && !lds_raised) { (void)hipFuncSetAttribute((const void*)qtrace_kernel<ST, AN_, NT_, CAP_, STG, ANY_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)(CAP_) * (NT_) * 4 + (size_t)RTW_TNODES_TOP_BUDGET * 32)); lds_raised = true; } \
+        hipLaunchKernelGGL((qtrace_kernel<ST, AN_, NT_, CAP_, STG, ANY_>), dim3(blocks), dim3(NT_), (DYN), stream, sc, rays, (uint32_t)n, hits11, shape, tri, occluded, q.staged_shape, carry); \
+    } while (0)
+#define RTW_LAUNCH_Q2(ST, AN_, NT_, CAP_, STG, DYN) do { if (any) RTW_LAUNCH_Q(ST, AN_, NT_, CAP_, STG, true, DYN); else RTW_LAUNCH_Q(ST, AN_, NT_, CAP_, STG, false, DYN); } while (0)
+#define RTW_LAUNCH_Q4(NT_, CAP_, STG, DYN)                                                                                                       \
+    do {                                                                                                                                        \
+        if (an) { if (stats) RTW_LAUNCH_Q2(true, true, NT_, CAP_, STG, DYN); else RTW_LAUNCH_Q2(false, true, NT_, CAP_, STG, DYN); }             \
+        else { if (stats) RTW_LAUNCH_Q2(true, false, NT_, CAP_, STG, DYN); else RTW_LAUNCH_Q2(false, false, NT_, CAP_, STG, DYN); }              \
+    } while (0)
+    if (nt == 1024) {
+        const size_t dyn = (size_t)RTW_GT_CAP_STAGED * 1024 * 4 + (size_t)q.staged_top * 32;
+        if (q.staged_all) RTW_LAUNCH_Q4(1024, RTW_GT_CAP_STAGED, 2, dyn);
+        else RTW_LAUNCH_Q4(1024, RTW_GT_CAP_STAGED, 1, dyn);
+    } else {
+        const size_t dyn = (size_t)RTW_GT_CAP * 256 * 4;
+        RTW_LAUNCH_Q4(256, RTW_GT_CAP, 0, dyn);
+    }
+#undef RTW_LAUNCH_Q4
+#undef RTW_LAUNCH_Q2
+#undef RTW_LAUNCH_Q
     return (int)hipGetLastError();
 }
 

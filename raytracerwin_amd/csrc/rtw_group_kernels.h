@@ -587,7 +587,9 @@ __device__ __forceinline__ LaneRay lane_ray_of(const Ray& r)
 // The box test (RRay::TestIntersectionWithAabb, Src/RRay.cpp:89-136) of a tame ray: (pair - origin) * reciprocal per axis as packed
 // operations, v_min / v_max (no NaN, no skipped axis: the same values as the reference's ternaries), then the conservative segment
 // clip.  A wave that holds a ray that is not tame takes the loop that also evaluates the test as written.
-template <bool STATS, int NT, int CAP, bool ALLDS>
+// ANY (the any-hit query of rtw_query_kernels.h; off everywhere else): a lane is done at its first accepted triangle -- it skips the rest of its
+// list and of its walk.  Up to that test its sequence of tests is the closest query's, so "it accepted one" is exactly "the closest query has a hit".
+template <bool STATS, int NT, int CAP, bool ALLDS, bool ANY = false>
 __device__ __forceinline__ bool lane_mesh_walk(const RtwShapeDev& sh, uint32_t* __restrict__ cand, const float4* __restrict__ lnodes, int ltop,
                                                const Ray& r, const LaneRay& q, bool go, bool prune, float& cur, f3& pos, int& leaf_out, Counters& ct)
 {
@@ -674,17 +676,20 @@ __device__ __forceinline__ bool lane_mesh_walk(const RtwShapeDev& sh, uint32_t* 
                     f3 cp; float dist;
                     if (triangle_test(r, cur, ta, tb, tc, td, cp, dist)) { cur = dist; pos = cp; leaf_out = leaf; any = true; }
                 }
-                mine = nmine; leaf = nleaf; ta = na; tb = nb; tc = nc; td = nd;
+                if (ANY) mine = nmine && !any; else mine = nmine;
+                leaf = nleaf; ta = na; tb = nb; tc = nc; td = nd;
             }
         }
         ncand = 0;
+        if (ANY && any) i = n_nodes;
         if (__ballot(i < n_nodes) == 0ull) break;
     }
     return any;
 }
 
 // staged_shape: the shape whose upper tree levels the block holds in LDS (lnodes, ltop), or -1
-template <bool STATS, bool AN, int NT, int CAP, bool ALLDS>
+// ANY: a lane whose query has a hit takes no further part (see lane_mesh_walk); only hit_shape >= 0 means anything afterwards
+template <bool STATS, bool AN, int NT, int CAP, bool ALLDS, bool ANY = false>
 __device__ __forceinline__ void lane_find_intersection(const RtwSceneDev* __restrict__ sc, uint32_t* __restrict__ cand, const float4* __restrict__ lnodes, int ltop, int staged_shape,
                                                        const Ray& ray, bool have, int first_shape,
                                                        int& hit_shape, int& hit_slot, f3& hit_pos, float& seg,
@@ -698,17 +703,18 @@ __device__ __forceinline__ void lane_find_intersection(const RtwSceneDev* __rest
         const RtwShapeDev& sh = sc->shapes[s];
         const int kind = AN ? sh.kind : RTW_SHAPE_MESH;
         float t0, t1;
-        const bool inbox = have && ((AN && kind == RTW_SHAPE_PLANE) ||
+        const bool live = ANY ? (have && hit_shape < 0) : have;
+        const bool inbox = live && ((AN && kind == RTW_SHAPE_PLANE) ||
                                     slab_exact(ray, sh.bmin[0], sh.bmin[1], sh.bmin[2], sh.bmax[0], sh.bmax[1], sh.bmax[2], t0, t1));
-        if (STATS && have && kind != RTW_SHAPE_PLANE) ct.boxes++;
+        if (STATS && live && kind != RTW_SHAPE_PLANE) ct.boxes++;
         if (__ballot(inbox) == 0ull) continue;
         float cur = seg; f3 pos = mk(0, 0, 0); int slot = -1;
         bool any = false;
         if (AN && kind != RTW_SHAPE_MESH) {
             if (inbox) any = analytic_test(sh, ray, seg, pos, cur, slot);
         } else if (sh.n_nodes > 0) {
-            if (ALLDS && s == staged_shape) any = lane_mesh_walk<STATS, NT, CAP, true>(sh, cand, lnodes, ltop, ray, q, inbox, prune, cur, pos, slot, ct);
-            else any = lane_mesh_walk<STATS, NT, CAP, false>(sh, cand, lnodes, s == staged_shape ? ltop : 0, ray, q, inbox, prune, cur, pos, slot, ct);
+            if (ALLDS && s == staged_shape) any = lane_mesh_walk<STATS, NT, CAP, true, ANY>(sh, cand, lnodes, ltop, ray, q, inbox, prune, cur, pos, slot, ct);
+            else any = lane_mesh_walk<STATS, NT, CAP, false, ANY>(sh, cand, lnodes, s == staged_shape ? ltop : 0, ray, q, inbox, prune, cur, pos, slot, ct);
         }
         if (any) {
             seg = cur; hit_shape = s; hit_slot = slot; hit_pos = pos;

@@ -152,6 +152,11 @@ struct rtw_context {
     bool ws_single = false;             // the group at hand is one pass: the limit does not apply (only hipMalloc can refuse it)
     int group_cap = 0;                  // > 0: groups of the current rtw_render_passes call hold at most this many passes (set after a refusal)
     int fallbacks = 0;                  // how many times a group was re-formed smaller after a refusal (rtw_context_memory_bytes' caller can see it: option-free diagnostics)
+    // ray queries on device buffers (rtw_trace_closest_device / rtw_trace_occluded_device)
+    int query_kernel = -1;              // option: 1 = qtrace_kernel, 0 = closest_kernel on the caller's buffers (the baseline and cross-check), -1 = the measured rule (query_uses_new_kernel)
+    int query_blocks = 0;               // option: > 0 = at most exactly this many blocks
+    void* d_query_ws = nullptr;         // "query_kernel" 0 only: stand-ins for the outputs closest_kernel writes and the caller did not ask for (grown on demand)
+    size_t query_ws_bytes = 0;
 };
 
 struct rtw_scene {
@@ -282,6 +287,7 @@ int rtw_context_destroy(rtw_context* ctx)
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     if (ctx->d_unit) release_device_table(ctx->device);
+    (void)hipFree(ctx->d_query_ws);
     (void)hipFree(ctx->d_workspace); (void)hipFree(ctx->d_gamma); (void)hipFree(ctx->d_lut); (void)hipFree(ctx->d_stats);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
     if (ctx->aux_stream) { (void)hipStreamSynchronize(ctx->aux_stream); (void)hipStreamDestroy(ctx->aux_stream); }
@@ -338,6 +344,8 @@ int rtw_context_set_option(rtw_context* ctx, const char* name, int value)
         ctx->group_max = value;
         return RTW_OK;
     }
+    if (std::strcmp(name, "query_kernel") == 0) { ctx->query_kernel = value < 0 ? -1 : (value ? 1 : 0); return RTW_OK; }
+    if (std::strcmp(name, "query_blocks") == 0) { ctx->query_blocks = value < 0 ? 0 : value; return RTW_OK; }
     if (std::strcmp(name, "hint_period") == 0) { ctx->hint_period = value < 1 ? 1 : value; return RTW_OK; }
     if (std::strcmp(name, "kernel_timing") == 0) {
         if (value && !ctx->timing_events[0]) for (int i = 0; i < 4; i++) HIP_TRY(hipEventCreate(&ctx->timing_events[i]));
@@ -939,6 +947,125 @@ int rtw_trace_closest(rtw_scene* scene, const float* rays, int64_t n, float* hit
     HIP_TRY(hipMemcpyAsync(shape, ds.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(tri, dt.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    return RTW_OK;
+}
+
+// ---- ray queries on the caller's device buffers ----
+namespace {
+struct QueryShape : rtw::QueryTuning { explicit QueryShape(const rtw_scene* scene); };
+QueryShape::QueryShape(const rtw_scene* scene)
+{
+    const rtw_context* cx = scene->ctx;
+    rtw::QueryTuning& q = *this;
+    q.cu_count = cx->cu_count; q.blocks = cx->query_blocks;
+    q.single_mesh = scene->meshes.size() == 1 && scene->meshes[0]->kind == RTW_SHAPE_MESH && !scene->meshes[0]->nodes.empty();
+    q.carry = scene->texture_carry;
+    for (size_t k = 0; k < scene->meshes.size(); k++)       // the first mesh's upper tree levels live in the blocks' LDS, as in the render path
+        if (scene->meshes[k]->kind == RTW_SHAPE_MESH && scene->meshes[k]->tnodes_top > 0) {
+            q.staged_shape = (int)k; q.staged_top = scene->meshes[k]->tnodes_top; q.staged_all = q.staged_top == (int)scene->meshes[k]->tnodes.size();
+            break;
+        }
+}
+// Which kernel a device query runs.  "query_kernel" -1 (the default) is the rule the interleaved A/B of tools/query_bench.py gave (profiles/query_experiments.md:
+// the new kernel wherever its median beat the old kernel's by more than the old kernel's own spread, the old kernel elsewhere):
+//   any-hit:  the new kernel on one-mesh scenes (1.1 to 2.1 x the old kernel on camera, bounce and shadow rays of all three meshes), the old one on scenes
+//             with analytic shapes (shadow rays of the default scene were 12 % slower);
+//   closest:  the old kernel -- the new one won by 8 to 19 % on bounce and shadow rays of trees that fit LDS whole, but not on camera rays (most miss the
+//             shape's box: the staging is not paid back), and lost 5 to 40 % on unitychan and on the default scene.
+bool query_uses_new_kernel(const rtw_scene* scene, bool any_hit)
+{
+    const int k = scene->ctx->query_kernel;
+    if (k >= 0) return k != 0;
+    return any_hit && QueryShape(scene).single_mesh;
+}
+// the old kernel (closest_kernel) writes all three outputs; the ones the caller left out go to the context's stand-in buffer
+int query_stand_ins(rtw_context* cx, int64_t n, float** hits, int32_t** shape, int32_t** tri)
+{
+    const size_t hb = ((size_t)n * 44 + 255) & ~(size_t)255, ib = ((size_t)n * 4 + 255) & ~(size_t)255;
+    const size_t need = (*hits ? 0 : hb) + (*shape ? 0 : ib) + (*tri ? 0 : ib);
+    if (need > cx->query_ws_bytes) {
+        HIP_TRY(hipStreamSynchronize(cx->stream));
+        if (cx->d_query_ws) { (void)hipFree(cx->d_query_ws); cx->d_query_ws = nullptr; cx->query_ws_bytes = 0; }
+        HIP_TRY(hipMalloc(&cx->d_query_ws, need));
+        cx->query_ws_bytes = need;
+    }
+    char* at = (char*)cx->d_query_ws;
+    if (!*hits) { *hits = (float*)at; at += hb; }
+    if (!*shape) { *shape = (int32_t*)at; at += ib; }
+    if (!*tri) { *tri = (int32_t*)at; at += ib; }
+    return RTW_OK;
+}
+int query_checks(rtw_scene* scene, const void* rays, int64_t n, bool some_output)
+{
+    if (!scene) return fail(RTW_ERR_INVALID, "scene is null");
+    if (!rays || n < 0 || !some_output) return fail(RTW_ERR_INVALID, n < 0 ? "n is negative" : (!rays ? "rays is null" : "every output is null"));
+    const int rc = need_committed(scene); if (rc != RTW_OK) return rc;
+    if (n > (int64_t)INT32_MAX) return fail(RTW_ERR_LIMIT, "at most 2^31 - 1 rays per query call");
+    return RTW_OK;
+}
+int occluded_device(rtw_scene* scene, const float* rays, int64_t n, uint8_t* occluded)
+{
+    rtw_context* cx = scene->ctx;
+    hipError_t e;
+    if (!query_uses_new_kernel(scene, true)) {
+        float* h = nullptr; int32_t *s = nullptr, *t = nullptr;
+        const int rc = query_stand_ins(cx, n, &h, &s, &t); if (rc != RTW_OK) return rc;
+        e = (hipError_t)rtw::launch_closest(scene->d_scene, rays, n, h, s, t, cx->stats_enabled, cx->stream);
+        if (e == hipSuccess) e = (hipError_t)rtw::launch_shape_to_byte(s, n, occluded, cx->stream);
+    } else {
+        e = (hipError_t)rtw::launch_query(scene->d_scene, rays, n, nullptr, nullptr, nullptr, occluded, QueryShape(scene), cx->stats_enabled, cx->stream);
+    }
+    if (e != hipSuccess) return hip_fail(e, "query kernel launch");
+    return RTW_OK;
+}
+}  // namespace
+
+int rtw_trace_closest_device(rtw_scene* scene, const void* rays_dev, int64_t n, void* hits11_dev, void* shape_dev, void* tri_dev)
+{
+    int rc = query_checks(scene, rays_dev, n, hits11_dev || shape_dev || tri_dev); if (rc != RTW_OK) return rc;
+    if (n == 0) return RTW_OK;
+    rtw_context* cx = scene->ctx;
+    float* h = (float*)hits11_dev; int32_t *s = (int32_t*)shape_dev, *t = (int32_t*)tri_dev;
+    hipError_t e;
+    if (!query_uses_new_kernel(scene, false)) {
+        rc = query_stand_ins(cx, n, &h, &s, &t); if (rc != RTW_OK) return rc;
+        e = (hipError_t)rtw::launch_closest(scene->d_scene, (const float*)rays_dev, n, h, s, t, cx->stats_enabled, cx->stream);
+    } else {
+        e = (hipError_t)rtw::launch_query(scene->d_scene, (const float*)rays_dev, n, h, s, t, nullptr, QueryShape(scene), cx->stats_enabled, cx->stream);
+    }
+    if (e != hipSuccess) return hip_fail(e, "query kernel launch");
+    return RTW_OK;
+}
+
+int rtw_trace_occluded_device(rtw_scene* scene, const void* rays_dev, int64_t n, void* occluded_dev)
+{
+    const int rc = query_checks(scene, rays_dev, n, occluded_dev != nullptr); if (rc != RTW_OK) return rc;
+    if (n == 0) return RTW_OK;
+    return occluded_device(scene, (const float*)rays_dev, n, (uint8_t*)occluded_dev);
+}
+
+int rtw_trace_occluded(rtw_scene* scene, const float* rays, int64_t n, uint8_t* occluded)
+{
+    int rc = query_checks(scene, rays, n, occluded != nullptr); if (rc != RTW_OK) return rc;
+    if (n == 0) return RTW_OK;
+    hipStream_t st = scene->ctx->stream;
+    DevBuf dr, dq;
+    HIP_TRY(dr.alloc((size_t)n * 28)); HIP_TRY(dq.alloc((size_t)n));
+    HIP_TRY(hipMemcpyAsync(dr.p, rays, (size_t)n * 28, hipMemcpyHostToDevice, st));
+    rc = occluded_device(scene, (const float*)dr.p, n, (uint8_t*)dq.p); if (rc != RTW_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(occluded, dq.p, (size_t)n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return RTW_OK;
+}
+
+int rtw_query_launch_shape(rtw_scene* scene, int64_t n, int any_hit, int32_t out2[2])
+{
+    if (!out2) return fail(RTW_ERR_INVALID, "null argument");
+    const int rc = query_checks(scene, out2, n, true); if (rc != RTW_OK) return rc;
+    if (!query_uses_new_kernel(scene, any_hit != 0)) { out2[0] = 256; out2[1] = (int32_t)((n + 255) / 256); return RTW_OK; }
+    int nt = 0; unsigned blocks = 0;
+    rtw::query_launch_shape(QueryShape(scene), n, &nt, &blocks);
+    out2[0] = nt; out2[1] = n > 0 ? (int32_t)blocks : 0;
     return RTW_OK;
 }
 
