@@ -166,6 +166,12 @@ __device__ __forceinline__ bool ray_is_tame_impl(const Ray& r)
            fabsf(r.o.x) < big && fabsf(r.o.y) < big && fabsf(r.o.z) < big;
 }
 
+// The pruned walks' segment clip reasons about the points Origin + t * Direction, t in [0, seg].  That holds for a tame ray whose segment
+// length is a number in [0, 1e15]: every intermediate of the triangle test is then finite.  A length that is NaN (for a segment of length 0
+// the sphere test divides 0 by 0 and reports a hit at distance NaN, as the reference's does), negative, infinite or huge lets the reference
+// accept triangles through comparisons that are all false, in boxes the clip would skip: a walk clips only while seg_clips(its segment).
+__device__ __forceinline__ bool seg_clips(float seg) { return seg >= 0.0f && seg <= 1.0e15f; }
+
 // ---- leaf: RRay::TestIntersectionWithTriangleAndFaceNormal (Src/RRay.cpp:147-213) ------------
 // N and d1 = dot(N, p0) come precomputed from the host (they depend on the triangle only).
 __device__ __forceinline__ bool triangle_test(const Ray& r, float cur_dist, const float4 a, const float4 b, const float4 c, float d1,
@@ -196,12 +202,13 @@ __device__ __forceinline__ bool triangle_test(const Ray& r, float cur_dist, cons
 // Reference order: box miss -> skip subtree; internal hit -> left child (i+1) then right; leaf hit ->
 // triangle test, shrink the segment on accept.  Equal-distance ties keep the LAST accepted leaf.
 // PRUNE adds a segment clip (tmin <= dist+eps, tmax >= -eps): it only skips boxes that cannot hold an
-// accepted hit, so the sequence of accepted hits -- and every output bit -- is unchanged.
+// accepted hit, so the sequence of accepted hits -- and every output bit -- is unchanged.  It is applied only while seg_clips(cur_dist).
 template <bool TAME, bool STATS>
 __device__ __forceinline__ bool tree_walk(const RtwSceneDev* __restrict__ sc, const RtwNode* __restrict__ nodes, const RtwTri* __restrict__ tris, int n_nodes, int n_tris,
                                           const Ray& r, bool prune, float& cur_dist, f3& hit_pos, int& hit_slot, Counters& ct)
 {
     float ix = 0.f, iy = 0.f, iz = 0.f, eps_t = 0.f;
+    prune = prune && seg_clips(cur_dist);
     if (TAME) {
         ix = 1.0f / r.d.x; iy = 1.0f / r.d.y; iz = 1.0f / r.d.z;
         // positional slack 2e-5 (scene units) expressed along the ray, plus a relative term
@@ -233,6 +240,7 @@ __device__ __forceinline__ bool tree_walk(const RtwSceneDev* __restrict__ sc, co
             f3 cp; float dist;
             if (triangle_test(r, cur_dist, a, b, c, d.x, cp, dist)) {
                 cur_dist = dist; hit_pos = cp; hit_slot = leaf; any = true;
+                prune = prune && seg_clips(dist);
             }
         }
         i = (hit && leaf < 0) ? i + 1 : skip;
@@ -259,6 +267,7 @@ __device__ __forceinline__ bool packet_walk(const RtwNode* nodes, const RtwTri* 
     const float4* nd4 = reinterpret_cast<const float4*>(nodes);
     const float4* tr4 = reinterpret_cast<const float4*>(tris);
     bool any = false;
+    bool clip = !EXACT && prune && seg_clips(cur_dist);      // this lane's segment can be clipped (see seg_clips)
     int i = 0;
     while (i < n_nodes) {
         const int iu = __builtin_amdgcn_readfirstlane(i);
@@ -278,7 +287,7 @@ __device__ __forceinline__ bool packet_walk(const RtwNode* nodes, const RtwTri* 
             tmax = fminf(fminf(fmaxf(x1, x2), fmaxf(y1, y2)), fmaxf(z1, z2));
         }
         bool hit = active && (tmax > tmin);
-        if (!EXACT && prune) hit = hit && !(tmin > cur_dist + (eps_t + 1.0e-4f * cur_dist)) && !(tmax < -eps_t);
+        if (clip) hit = hit && !(tmin > cur_dist + (eps_t + 1.0e-4f * cur_dist)) && !(tmax < -eps_t);
         if (STATS) ct.boxes += active ? 1u : 0u;
         const bool any_hit = __ballot(hit) != 0ull;
         if (leaf >= 0) {
@@ -287,7 +296,7 @@ __device__ __forceinline__ bool packet_walk(const RtwNode* nodes, const RtwTri* 
                 if (hit) {
                     if (STATS) ct.tris++;
                     f3 cp; float dist;
-                    if (triangle_test(r, cur_dist, a, b, c, d.x, cp, dist)) { cur_dist = dist; hit_pos = cp; hit_slot = leaf; any = true; }
+                    if (triangle_test(r, cur_dist, a, b, c, d.x, cp, dist)) { cur_dist = dist; hit_pos = cp; hit_slot = leaf; any = true; clip = clip && seg_clips(dist); }
                 }
             }
             i = skip;
@@ -810,7 +819,7 @@ __device__ __forceinline__ Ray camera_ray_xy(const RtwRenderParams& p, int x, in
 // affects speed only.
 __device__ __forceinline__ uint32_t gamma_channel(const float* __restrict__ thr, float c)
 {
-    if (!(c > 0.0f)) return 0u;
+    if (!(c > 0.0f)) return c == -__builtin_inff() ? 255u : 0u;       // powf(-inf, 1 / 2.2f) is +inf: the reference packs 255
     if (c >= 1.0f) return 255u;
     int k = (int)(__builtin_amdgcn_exp2f(__builtin_amdgcn_logf(c) * (1.0f / 2.2f)) * 255.0f);
     k = k < 0 ? 0 : (k > 255 ? 255 : k);
@@ -829,7 +838,7 @@ __device__ __forceinline__ int gamma_guess(float c)
 // the largest k with thr[k] <= c, given the guess g in 0..254 and the two table entries around it
 __device__ __forceinline__ uint32_t gamma_fix(const float* __restrict__ thr, float c, int g, float t0, float t1)
 {
-    if (!(c > 0.0f)) return 0u;
+    if (!(c > 0.0f)) return c == -__builtin_inff() ? 255u : 0u;       // powf(-inf, 1 / 2.2f) is +inf: the reference packs 255
     if (c >= 1.0f) return 255u;
     if (t0 <= c && !(t1 <= c)) return (uint32_t)g;          // thr[g] <= c < thr[g + 1]: the guess was right (almost always)
     int k = g;
@@ -1064,7 +1073,7 @@ __device__ __forceinline__ bool shade_hit_step(const RtwSceneDev* __restrict__ s
             if (sh.kind == RTW_SHAPE_PLANE) { more = true; continue; }
             tested++;
             if (!slab_exact(ray, sh.bmin[0], sh.bmin[1], sh.bmin[2], sh.bmax[0], sh.bmax[1], sh.bmax[2], t0, t1)) continue;
-            if (cull && sh.kind == RTW_SHAPE_MESH && (t0 > seg + (eps_t + 1.0e-4f * seg) || t1 < -eps_t)) continue;     // (meshes only: their walk applies the same cull)
+            if (cull && seg_clips(seg) && sh.kind == RTW_SHAPE_MESH && (t0 > seg + (eps_t + 1.0e-4f * seg) || t1 < -eps_t)) continue;     // (meshes only: their walk applies the same cull)
             more = true;
         }
         if (STATS && !more) { ct.rays++; ct.boxes += tested; }       // (a ray that goes on to the trace kernel is counted there)

@@ -206,7 +206,7 @@ __device__ __forceinline__ bool group_lead_query(const RtwSceneDev* __restrict__
         if (sh.kind == RTW_SHAPE_PLANE) { more = true; continue; }
         tested++;
         if (!slab_exact(ray, sh.bmin[0], sh.bmin[1], sh.bmin[2], sh.bmax[0], sh.bmax[1], sh.bmax[2], t0, t1)) continue;
-        if (cull && sh.kind == RTW_SHAPE_MESH && (t0 > seg + (eps_t + 1.0e-4f * seg) || t1 < -eps_t)) continue;     // (meshes only: their walk applies the same clip)
+        if (cull && seg_clips(seg) && sh.kind == RTW_SHAPE_MESH && (t0 > seg + (eps_t + 1.0e-4f * seg) || t1 < -eps_t)) continue;     // (meshes only: their walk applies the same clip)
         more = true;
     }
     if (STATS && !more) { ct.rays++; ct.boxes += tested; }       // (a ray that goes on is counted by the trace kernel)
@@ -266,7 +266,8 @@ __global__ __launch_bounds__(256) void gsky_kernel(const float* __restrict__ gam
 // The bins walk of one mesh for up to four camera rays per lane at once (the sub-samples of a pixel and / or the same pixel in several passes: they all start
 // at the camera and differ by their jitter only): an entry's leaf box and triangle record are fetched and broadcast once, every ray keeps its own
 // segment and meets the entries in the list's order (= preorder), so each ray's sequence of tests -- and every bit of its result -- is what it is
-// when the rays are walked one after the other.  All rays tame (the caller checks).
+// when the rays are walked one after the other.  All rays tame (the caller checks), and camera rays: unit directions and segments that start
+// at the camera's 1000 and only shrink to hit distances, so seg_clips() holds throughout.
 template <bool STATS>
 __device__ __forceinline__ void bins_walk_rays(const RtwShapeDev& sh, const uint32_t* __restrict__ boff, const uint32_t* __restrict__ bent, int bin, int lane, int nr, bool prune,
                                                const f3 o, const f3 (&d)[4], const bool (&act)[4], float (&cur)[4], f3 (&pos)[4], int (&slot_hit)[4], bool (&any)[4], Counters& ct)
@@ -463,6 +464,7 @@ __global__ __launch_bounds__(256, RTW_GPRIMARY_MINB) void gprimary_kernel(const 
                         const float4* tr4 = reinterpret_cast<const float4*>(sh.tris);
                         const float ix = (!tame && skx) ? 0.0f : 1.0f / ray.d.x, iy = (!tame && sky) ? 0.0f : 1.0f / ray.d.y, iz = (!tame && skz) ? 0.0f : 1.0f / ray.d.z;
                         const float eps_t = 2.0e-5f * fmaxf(fabsf(ix), fmaxf(fabsf(iy), fabsf(iz)));
+                        bool clip = prune && seg_clips(cur);         // (an earlier shape's hit may have left a segment the clip does not hold for)
                         // 64 entries at a time: lane j fetches entry j's leaf box and triangle record (all loads in flight together),
                         // then the wave goes through the entries in order and every lane tests its own ray against the broadcast record
                         for (int ec = e0; ec < e1; ec += 64) {
@@ -481,7 +483,7 @@ __global__ __launch_bounds__(256, RTW_GPRIMARY_MINB) void gprimary_kernel(const 
                                 const float tmin = fmaxf(fmaxf(fminf(x1, x2), fminf(y1, y2)), fminf(z1, z2));
                                 const float tmax = fminf(fminf(fmaxf(x1, x2), fmaxf(y1, y2)), fmaxf(z1, z2));
                                 bool hit = active && (tmax > tmin);
-                                if (prune) hit = hit && !(tmin > cur + (eps_t + 1.0e-4f * cur)) && !(tmax < -eps_t);
+                                if (clip) hit = hit && !(tmin > cur + (eps_t + 1.0e-4f * cur)) && !(tmax < -eps_t);
                                 if (any_untame) {                // wave-uniform: RRay::TestIntersectionWithAabb as written for the lanes that need it
                                     float emin = -FLT_MAX, emax = FLT_MAX;
                                     if (!skx) { emin = ref_max(emin, ref_min(x1, x2)); emax = ref_min(emax, ref_max(x1, x2)); }
@@ -499,7 +501,7 @@ __global__ __launch_bounds__(256, RTW_GPRIMARY_MINB) void gprimary_kernel(const 
                                 if (hit) {
                                     if (STATS) ct.tris++;
                                     f3 cp; float dist;
-                                    if (triangle_test(ray, cur, a, bq, c, d1, cp, dist)) { cur = dist; pos = cp; slot_hit = leaf; any = true; }
+                                    if (triangle_test(ray, cur, a, bq, c, d1, cp, dist)) { cur = dist; pos = cp; slot_hit = leaf; any = true; clip = clip && seg_clips(dist); }
                                 }
                             }
                         }
@@ -600,12 +602,13 @@ __device__ __forceinline__ bool lane_mesh_walk(const RtwShapeDev& sh, uint32_t* 
     const bool any_untame = __ballot(go && !q.tame) != 0ull;
     const rtw_v2f ox = { q.o.x, q.o.x }, oy = { q.o.y, q.o.y }, oz = { q.o.z, q.o.z };
     const rtw_v2f vx = { q.ix, q.ix }, vy = { q.iy, q.iy }, vz = { q.iz, q.iz };
-    const float neg_eps = prune ? -q.eps_t : -INFINITY;
     bool any = false;
     int i = go ? 0 : n_nodes;
     int ncand = 0;
     for (;;) {
-        const float far_t = prune ? cur + (q.eps_t + 1.0e-4f * cur) : INFINITY;       // the segment only changes in the triangle phase below
+        const bool clip = prune && seg_clips(cur);                                   // the segment only changes in the triangle phase below
+        const float far_t = clip ? cur + (q.eps_t + 1.0e-4f * cur) : INFINITY;
+        const float neg_eps = clip ? -q.eps_t : -INFINITY;
         // ---- walk: every lane steps through its own records until all are done or some lane's list is full ----
         if (!any_untame) {
             for (;;) {
@@ -931,8 +934,9 @@ __global__ __launch_bounds__(NT) void gtrace_persist_kernel(const RtwSceneDev* _
         RTW_TM(const unsigned long long tm_e1 = __builtin_amdgcn_s_memtime(); tm_refill += tm_e1 - tm_e0;)
         if (__ballot(have) == 0ull) break;
         const bool any_untame = __ballot(have && !tame) != 0ull;
-        const float far_t = prune ? cur + (eps_t + 1.0e-4f * cur) : INFINITY;
-        const float neg_eps = prune ? -eps_t : -INFINITY;
+        const bool clip = prune && seg_clips(cur);         // (the segment only changes in the triangle phase below)
+        const float far_t = clip ? cur + (eps_t + 1.0e-4f * cur) : INFINITY;
+        const float neg_eps = clip ? -eps_t : -INFINITY;
         // ---- walk ----
         if (!any_untame) {
             const rtw_v2f ox = { r.o.x, r.o.x }, oy = { r.o.y, r.o.y }, oz = { r.o.z, r.o.z };

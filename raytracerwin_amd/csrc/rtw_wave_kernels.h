@@ -125,11 +125,12 @@ __device__ __forceinline__ bool wave_walk_flat(const FlatSrc& src, uint32_t* __r
     const int n0 = src.n[0], n1 = src.n[1], n2 = src.n[2];
     bool any = false;
     int ncand = 0;
+    bool clip = !EXACT && prune && seg_clips(cur_dist);      // (the segment only changes in wave_triangles)
     for (int t0 = 0; t0 < n2; t0 += 64) {
         float far_t = cur_dist + (fr.eps_t + 1.0e-4f * cur_dist);
         const int i2 = t0 + lane;
         const bool v2 = i2 < n2;
-        const bool h2 = v2 && flat_box_hit<EXACT>(src.lvl[2], i2, fr, prune, far_t);
+        const bool h2 = v2 && flat_box_hit<EXACT>(src.lvl[2], i2, fr, clip, far_t);
         if (STATS) ct.boxes += v2 ? 1u : 0u;
         const unsigned long long m2 = __ballot(h2);
         if (m2 == 0ull) continue;
@@ -141,7 +142,7 @@ __device__ __forceinline__ bool wave_walk_flat(const FlatSrc& src, uint32_t* __r
             const int g = g2 + lane;
             const int i1 = (g < c2 ? (int)lldu(l2, g >> 4) : 0) * 16 + (g & 15);
             const bool v1 = g < c2 && i1 < n1;
-            const bool h1 = v1 && flat_box_hit<EXACT>(src.lvl[1], i1, fr, prune, far_t);
+            const bool h1 = v1 && flat_box_hit<EXACT>(src.lvl[1], i1, fr, clip, far_t);
             if (STATS) ct.boxes += v1 ? 1u : 0u;
             const unsigned long long m1 = __ballot(h1);
             if (m1 == 0ull) continue;
@@ -153,7 +154,7 @@ __device__ __forceinline__ bool wave_walk_flat(const FlatSrc& src, uint32_t* __r
                 const int gg = g1 + lane;
                 const int i0 = (gg < c1 ? (int)lldu(l1, gg >> 4) : 0) * 16 + (gg & 15);
                 const bool v0 = gg < c1 && i0 < n0;
-                const bool h0 = v0 && flat_box_hit<EXACT>(src.lvl[0], i0, fr, prune, far_t);
+                const bool h0 = v0 && flat_box_hit<EXACT>(src.lvl[0], i0, fr, clip, far_t);
                 if (STATS) ct.boxes += v0 ? 1u : 0u;
                 const unsigned long long m0 = __ballot(h0);
                 if (m0 == 0ull) continue;
@@ -164,6 +165,7 @@ __device__ __forceinline__ bool wave_walk_flat(const FlatSrc& src, uint32_t* __r
                     wave_triangles<STATS>(src.tris, lc, ncand, r, cur_dist, hit_pos, hit_slot, any, ct);
                     wave_lds_sync();
                     ncand = 0;
+                    clip = clip && seg_clips(cur_dist);
                     far_t = cur_dist + (fr.eps_t + 1.0e-4f * cur_dist);
                 }
             }
@@ -381,6 +383,7 @@ __global__ __launch_bounds__(256) void primary_bins_kernel(const RtwSceneDev* __
                     const float4* tr4 = reinterpret_cast<const float4*>(sh.tris);
                     const float ix = (!tame && skx) ? 0.0f : 1.0f / ray.d.x, iy = (!tame && sky) ? 0.0f : 1.0f / ray.d.y, iz = (!tame && skz) ? 0.0f : 1.0f / ray.d.z;
                     const float eps_t = 2.0e-5f * fmaxf(fabsf(ix), fmaxf(fabsf(iy), fabsf(iz)));
+                    bool clip = prune && seg_clips(cur);         // (an earlier shape's hit may have left a segment the clip does not hold for)
                     const int lane = lane_id();
                     // 64 entries at a time: lane j fetches entry j's leaf box and triangle record (all loads in flight together),
                     // then the wave goes through the entries in order and every lane tests its own ray against the broadcast record
@@ -400,7 +403,7 @@ __global__ __launch_bounds__(256) void primary_bins_kernel(const RtwSceneDev* __
                             const float tmin = fmaxf(fmaxf(fminf(x1, x2), fminf(y1, y2)), fminf(z1, z2));
                             const float tmax = fminf(fminf(fmaxf(x1, x2), fmaxf(y1, y2)), fmaxf(z1, z2));
                             bool hit = active && (tmax > tmin);
-                            if (prune) hit = hit && !(tmin > cur + (eps_t + 1.0e-4f * cur)) && !(tmax < -eps_t);
+                            if (clip) hit = hit && !(tmin > cur + (eps_t + 1.0e-4f * cur)) && !(tmax < -eps_t);
                             if (any_untame) {                // wave-uniform: RRay::TestIntersectionWithAabb as written for the lanes that need it
                                 float emin = -FLT_MAX, emax = FLT_MAX;
                                 if (!skx) { emin = ref_max(emin, ref_min(x1, x2)); emax = ref_min(emax, ref_max(x1, x2)); }
@@ -418,7 +421,7 @@ __global__ __launch_bounds__(256) void primary_bins_kernel(const RtwSceneDev* __
                             if (hit) {
                                 if (STATS) ct.tris++;
                                 f3 cp; float dist;
-                                if (triangle_test(ray, cur, a, b, c, d1, cp, dist)) { cur = dist; pos = cp; slot = leaf; any = true; }
+                                if (triangle_test(ray, cur, a, b, c, d1, cp, dist)) { cur = dist; pos = cp; slot = leaf; any = true; clip = clip && seg_clips(dist); }
                             }
                         }
                     }

@@ -78,6 +78,211 @@ def make_rays(bounds, n, rng):
     return np.concatenate(rays).astype(np.float32)
 
 
+# ---- rays aimed at the edges of the analytic shapes (scene "edges" of tests/scenes.py) ----
+EDGE_FAMILIES = ("generic", "centre", "from_centre", "surface_in", "surface_out", "tangent", "segment_end",
+                 "plane_parallel", "plane_inside", "plane_near_parallel", "plane_origin_on", "plane_behind",
+                 "capsule_axis", "capsule_parallel", "capsule_seam", "capsule_perp_end",
+                 "tri_vertex", "tri_edge", "tri_behind", "tri_inplane", "odd")
+EDGE_ULP_FAMILIES = ("tangent", "segment_end", "capsule_parallel", "capsule_seam", "tri_vertex", "tri_edge")   # hit or miss decided within a few ulps
+EDGE_ULPS = (0, 1, 2, 8, 1000)
+EDGE_DISTANCE_ULPS = (0, 1, -1, 4, -4)
+ULP = 2.0 ** -23
+
+
+def _step32(x, k):
+    """the float32 value k representable steps above (k > 0) or below (k < 0) float32(x)"""
+    x = np.float32(x)
+    for _ in range(abs(k)):
+        x = np.nextafter(x, np.float32(np.inf if k > 0 else -np.inf), dtype=np.float32)
+    return x
+
+
+def make_edge_rays(scene, rng):
+    """Rays drawn per shape of `scene` at the places where a shape test decides within a few ulps: (rays (n, 7) float32,
+    family (n,) int32 indices into EDGE_FAMILIES, target (n,) int32 shape index the ray was aimed at)."""
+    out = []                                                        # (origin, direction, distance, family, target)
+
+    def emit(fam, tgt, o, d, dist=1000.0):
+        out.append((np.asarray(o, np.float64), np.asarray(d, np.float64), float(dist), EDGE_FAMILIES.index(fam), tgt))
+
+    def unit(v):
+        return v / np.linalg.norm(v)
+
+    def rand_unit(towards=None, least=0.3):
+        while True:
+            u = unit(rng.normal(size=3))
+            if towards is None or u @ towards >= least:
+                return u
+
+    def perp(u):
+        while True:
+            w = np.cross(u, rng.normal(size=3))
+            if np.linalg.norm(w) > 1e-3:
+                return unit(w)
+
+    def basis(n):
+        """two unit vectors that span the plane of normal n; exact axes for an axis-aligned n"""
+        k = int(np.argmax(np.abs(n)))
+        if abs(abs(n[k]) - 1.0) < 1e-12:
+            return np.eye(3)[(k + 1) % 3], np.eye(3)[(k + 2) % 3]
+        t1 = unit(np.cross(n, np.eye(3)[(k + 1) % 3]))
+        return t1, np.cross(n, t1)
+
+    def sphere_like(tgt, c, radius, hemi=None, generic=10):
+        """a sphere, or a capsule's end cap (hemi: the axis direction that points out of the capsule there)"""
+        c, r = np.asarray(c, np.float64), abs(float(radius))
+        size = max(r, 0.25)
+        for _ in range(4):
+            u = rand_unit(hemi)
+            emit("centre", tgt, c + u * (r + size * rng.uniform(1, 4)), -u)
+        for _ in range(2):
+            emit("from_centre", tgt, c, rand_unit(hemi))
+        for _ in range(3):
+            u = rand_unit(hemi)
+            emit("surface_in", tgt, c + u * r, -u)
+            u = rand_unit(hemi)
+            emit("surface_out", tgt, c + u * r, u)
+        for j in EDGE_ULPS:                                         # closest approach to the centre: radius * (1 +- j * 2^-23)
+            for s in (1.0, -1.0):
+                for _ in range(6):
+                    u = rand_unit(hemi)
+                    w = perp(u)
+                    p = c + u * (r * (1.0 + s * j * ULP))
+                    emit("tangent", tgt, p - w * (size * rng.uniform(1, 3)), w)
+        for k in EDGE_DISTANCE_ULPS:                                # a segment that ends at the analytic hit distance, moved by k ulps
+            for _ in range(6):
+                u = rand_unit(hemi)
+                o = (c + u * (r + size * rng.uniform(1, 4))).astype(np.float32).astype(np.float64)
+                emit("segment_end", tgt, o, -u, _step32(np.linalg.norm(o - c) - r, k))
+        for _ in range(generic):
+            o = c + rand_unit(hemi, -1.0) * (r + size * rng.uniform(1, 4))
+            emit("generic", tgt, o, unit(c + rand_unit() * (size * rng.uniform(0, 2.5)) - o), rng.uniform(0.5, 8) * size)
+
+    for tgt, sh in enumerate(scene):
+        if sh[0] == "sphere":
+            sphere_like(tgt, sh[1], sh[2])
+        elif sh[0] == "plane":
+            n, p = np.asarray(sh[1], np.float64), np.asarray(sh[2], np.float64)
+            nn = unit(n) if np.linalg.norm(n) > 0 else np.array([0.0, 1.0, 0.0])        # a zero normal: aimed at as if it were a y-plane
+            t1, t2 = basis(nn)
+            on = lambda: p + t1 * rng.uniform(-4, 4) + t2 * rng.uniform(-4, 4)           # noqa: E731
+            inside = lambda: (lambda a: t1 * np.cos(a) + t2 * np.sin(a))(rng.uniform(0, 2 * np.pi))   # noqa: E731
+            for _ in range(4):
+                emit("plane_parallel", tgt, on() + nn * rng.uniform(0.5, 2), inside())
+                emit("plane_inside", tgt, on(), inside())
+            for j in (1, 2, 4, 5, 8, 1000):                         # |normal . direction| around the test's 1e-6
+                for side in (1.0, -1.0):
+                    for heading in (1.0, -1.0):
+                        for _ in range(2):
+                            emit("plane_near_parallel", tgt, on() + nn * (side * rng.uniform(0.5, 2)), unit(inside() - nn * (heading * j * ULP)), 1e30)
+            for _ in range(6):
+                emit("plane_origin_on", tgt, on(), rand_unit())
+            for _ in range(4):
+                emit("plane_behind", tgt, on() - nn * rng.uniform(0.5, 2), rand_unit(nn))
+                emit("plane_behind", tgt, on() - nn * rng.uniform(0.5, 2), -rand_unit(nn))
+            for k in EDGE_DISTANCE_ULPS:
+                for _ in range(4):
+                    o = (on() + nn * rng.uniform(0.5, 2)).astype(np.float32).astype(np.float64)
+                    d = -rand_unit(nn)
+                    emit("segment_end", tgt, o, d, _step32(((p - o) @ nn) / (d @ nn), k))
+            for _ in range(10):
+                emit("generic", tgt, on() + nn * rng.uniform(-2, 2), rand_unit(), rng.uniform(0.5, 8))
+        elif sh[0] == "capsule":
+            a, b, r = np.asarray(sh[1], np.float64), np.asarray(sh[2], np.float64), float(sh[3])
+            length = np.linalg.norm(b - a)
+            e = unit(b - a) if length > 0 else np.array([0.0, 0.0, 1.0])
+            size = max(r, 0.25)
+            sphere_like(tgt, a, r, -e, generic=0)
+            sphere_like(tgt, b, r, e, generic=0)
+            for end, out_dir in ((a, -e), (b, e)):
+                emit("capsule_axis", tgt, end + out_dir * (r + rng.uniform(1, 3)), -out_dir)                                # along the axis, through both caps
+                emit("capsule_axis", tgt, end + out_dir * (r + rng.uniform(1, 3)) + perp(e) * (r * 0.5), -out_dir)
+                for j in EDGE_ULPS:
+                    for s in (1.0, -1.0):
+                        for _ in range(2):
+                            w = perp(e)
+                            emit("capsule_parallel", tgt, end + out_dir * (r + rng.uniform(0.5, 2)) + w * (r * (1.0 + s * j * ULP)), -out_dir)
+                            # tangent to the surface at a point of the seam between side and cap, heading anywhere in the tangent plane
+                            w, ang = perp(e), rng.uniform(0, 2 * np.pi)
+                            d = unit(e * np.cos(ang) + np.cross(e, w) * np.sin(ang))
+                            emit("capsule_seam", tgt, end + w * (r * (1.0 + s * j * ULP)) - d * (size * rng.uniform(1, 3)), d)
+                for j in (0, 1, -1, 8, -8):                         # perpendicular to the axis at its end, a few ulps to either side of the seam
+                    w = perp(e)
+                    emit("capsule_perp_end", tgt, end + e * (j * ULP * max(length, 1.0)) + w * (r + size * rng.uniform(1, 3)), -w)
+            for _ in range(10):
+                o = a + (b - a) * rng.uniform(-0.2, 1.2) + rand_unit() * (r + size * rng.uniform(1, 4))
+                emit("generic", tgt, o, unit(a + (b - a) * rng.uniform(-0.2, 1.2) + rand_unit() * (size * rng.uniform(0, 2.5)) - o), rng.uniform(0.5, 8) * size)
+        elif sh[0] == "triangle":
+            v = [np.asarray(q, np.float64) for q in sh[1:4]]
+            n = unit(np.cross(v[1] - v[0], v[2] - v[0]))            # the side the reference sees it from
+            g = (v[0] + v[1] + v[2]) / 3.0
+            step = 4.0 * ULP                                         # coordinates of magnitude 2 - 4: one ulp of a position
+            front = lambda aim: aim + n * rng.uniform(1, 3) + perp(n) * rng.uniform(0, 0.5)     # noqa: E731
+            for i in range(3):
+                mid = (v[i] + v[(i + 1) % 3]) / 2.0
+                outward = unit(np.cross(v[(i + 1) % 3] - v[i], n))
+                for j in EDGE_ULPS:
+                    for s in (1.0, -1.0):
+                        for _ in range(2):
+                            aim = v[i] + unit(v[i] - g) * (s * j * step)
+                            o = front(aim)
+                            emit("tri_vertex", tgt, o, unit(aim - o))
+                            aim = mid + outward * (s * j * step)
+                            o = front(aim)
+                            emit("tri_edge", tgt, o, unit(aim - o))
+            for _ in range(3):
+                o = g - n * rng.uniform(1, 3) + perp(n) * rng.uniform(0, 0.3)
+                emit("tri_behind", tgt, o, unit(g - o))
+                w = perp(n)
+                emit("tri_inplane", tgt, g + w * 3.0, -w)
+            emit("tri_inplane", tgt, g, -n)                          # origin in the triangle, looking down and up
+            emit("tri_inplane", tgt, g, n)
+            for k in EDGE_DISTANCE_ULPS:
+                for _ in range(4):
+                    o = front(g).astype(np.float32).astype(np.float64)
+                    d = unit(g - o)
+                    emit("segment_end", tgt, o, d, _step32(((v[0] - o) @ n) / (d @ n), k))
+            for _ in range(10):
+                o = g + rand_unit() * rng.uniform(1, 4)
+                emit("generic", tgt, o, unit(g + rand_unit() * rng.uniform(0, 2) - o), rng.uniform(0.5, 8))
+        else:
+            bounds = np.load(os.path.join(OUT, "mesh_%s.npz" % sh[1]))["shape_bounds"]
+            for ray in make_rays(bounds, 40, rng):
+                emit("generic", tgt, ray[:3], ray[3:6], ray[6])
+    # the odd rays, sent at one shape of each kind (the last of its kind in the list): a ray that hits it, spoiled in one way
+    last = {sh[0]: k for k, sh in enumerate(scene)}
+    for kind, tgt in sorted(last.items()):
+        sh = scene[tgt]
+        if kind == "plane":
+            tgt = max(k for k, s in enumerate(scene) if s[0] == "plane" and np.linalg.norm(s[1]) > 0)
+            sh = scene[tgt]
+            aim, o = np.asarray(sh[2], np.float64), np.asarray(sh[2], np.float64) + unit(np.asarray(sh[1], np.float64)) * 2 + np.array([0.3, 0.0, 0.2])
+        elif kind == "mesh":
+            aim, o = np.array([0.0, 0.0, 0.0]), np.array([0.5, 0.3, 6.0])
+        elif kind == "triangle":
+            v = [np.asarray(q, np.float64) for q in sh[1:4]]
+            aim = (v[0] + v[1] + v[2]) / 3.0
+            o = aim + unit(np.cross(v[1] - v[0], v[2] - v[0])) * 2
+        else:
+            aim = np.asarray(sh[1], np.float64) if kind == "sphere" else (np.asarray(sh[1], np.float64) + np.asarray(sh[2], np.float64)) / 2
+            o = aim + np.array([0.4, 0.5, 3.0])
+        d = unit(aim - o)
+        nan, inf = np.nan, np.inf
+        emit("odd", tgt, o, d)                                       # (the unspoiled ray)
+        emit("odd", tgt, o * [1, nan, 1], d)
+        emit("odd", tgt, o, d * [1, 1, nan])
+        emit("odd", tgt, o + [inf, 0, 0], d)
+        emit("odd", tgt, o, d + [0, inf, 0])
+        emit("odd", tgt, o, d * 0)
+        emit("odd", tgt, o, d, 0.0)
+        emit("odd", tgt, o, d, -1.0)
+        emit("odd", tgt, o, d, 1e-40)
+        emit("odd", tgt, o, d * 1e-3)
+        emit("odd", tgt, o, d * 1e3)
+    rays = np.array([np.r_[o, d, dist] for o, d, dist, _, _ in out]).astype(np.float32)
+    return rays, np.array([f for *_, f, _ in out], np.int32), np.array([t for *_, t in out], np.int32)
+
+
 def golden_mesh(name, tmp):
     pre = os.path.join(tmp, name)
     run(["dump_mesh", obj_path(name), pre])
@@ -222,6 +427,100 @@ def golden_scene_closest(tag, n, tmp, rng, mesh_bounds):
                         shape=r[:, 11].copy().view(np.int32))
 
 
+def golden_edges(tmp):
+    """scene "edges" under make_edge_rays' rays (a generator of its own: no other fixture's draw moves)"""
+    scene = SC.SCENES["edges"]()
+    sp = write_scene_file(scene, tmp, "edges")
+    rays, family, target = make_edge_rays(scene, np.random.default_rng(20261021))
+    assert len(rays) <= 4000
+    rp, hp = os.path.join(tmp, "edge_rays.bin"), os.path.join(tmp, "edge_hits.bin")
+    rays.tofile(rp)
+    run(["closest", sp, rp, len(rays), hp])
+    r = np.fromfile(hp, np.float32).reshape(-1, 13)
+    np.savez_compressed(os.path.join(OUT, "sceneclosest_edges.npz"), scene="edges", rays=rays, hit=r[:, :11].copy(),
+                        shape=r[:, 11].copy().view(np.int32), family=family, target=target)
+
+
+# ---- textures of awkward shapes: tests/golden/oddtex/ (a quad per material) and texsample_oddtex_m{k}.npz ----
+ODDTEX = ((1, 1, 3), (1, 9, 4), (7, 1, 3), (5, 3, 4), (33, 17, 3))                          # width, height, channels of material k's texture
+ODDTEX_UV = ((0, 0, 1, 1), (-0.5, 0, 1.5, 1), (0, -1, 1, 2), (-1, -1, 2, 2), (0.25, 0, 3, 1))   # u0, v0, u1, v1 over material k's quad
+ODDTEX_CENTRES = ((-2.2, 1.2), (0.0, 1.2), (2.2, 1.2), (-1.1, -1.2), (1.1, -1.2))
+
+
+def oddtex_texels(k):
+    """(h, w, channels) uint8: every texel of the texture differs from every other, and so does every alpha"""
+    w, h, c = ODDTEX[k]
+    rng = np.random.default_rng(7000 + k)
+    while True:
+        px = rng.integers(0, 256, (h, w, c)).astype(np.uint8)
+        if c == 4:
+            px[:, :, 3] = rng.choice(256, h * w, replace=False).reshape(h, w)
+        if len(np.unique(px[:, :, :3].reshape(-1, 3), axis=0)) == h * w:
+            return px
+
+
+def oddtex_uv(k, rng):
+    """about 300 uv pairs for material k: every texel column and row with the neighbouring floats on either side, wrap-around edges"""
+    w, h, _ = ODDTEX[k]
+    f = np.float32
+    edge = np.array([[0, 0], [1, 1], [0.5, 0.5], [-1e-9, 0.25], [0.25, -1e-9], [1.0, 0.0], [0.999999, 0.999999],
+                     [2.0, -3.0], [1 / 511.0, 2 / 511.0], [255 / 255.0, 17 / 255.0]], f)
+
+    def grid(n):
+        if n == 1:
+            return [f(0), f(0.5), f(1)]
+        at = [f(i) / f(n - 1) for i in range(n)]
+        return [x for a in at for x in (np.nextafter(a, f(-1)), a, np.nextafter(a, f(2)))]
+    U, V = grid(w), grid(h)
+    pairs = [(U[i], V[(i * 7 + 3) % len(V)]) for i in range(len(U))] + [(U[(i * 5 + 1) % len(U)], V[i]) for i in range(len(V))]
+    special = [f(1e-9), f(-1e-9), f(-0.0), f(-1), f(-2), f(-3), f(1 - 2.0 ** -24), f(8388607.5), f(1e9), f(-1e9), f(0), f(1)]
+    pairs += [p for s in special for p in ((s, f(0.3)), (f(0.3), s), (s, s))]
+    uv = np.concatenate([edge, np.array(pairs, f)])
+    return np.concatenate([uv, rng.uniform(-2.5, 2.5, (max(0, 300 - len(uv)), 2)).astype(f)])
+
+
+def golden_oddtex(tmp):
+    """Writes tests/golden/oddtex/ (oddtex.obj, oddtex.mtl, t{k}.png) and, through the reference's own loader and sampler,
+    texsample_oddtex_m{k}.npz.  RGB files by the reference's PNG writer (harness `savepng`), RGBA files (it writes no alpha) by Pillow."""
+    from PIL import Image
+    d = os.path.join(OUT, "oddtex")
+    os.makedirs(d, exist_ok=True)
+    obj, mtl = ["# a quad per material, facing +z (tilted: a triangle in a z = const plane has a box no ray enters)", "mtllib oddtex.mtl", "vn 0 0 1"], []
+    for k, ((w, h, c), (u0, v0, u1, v1), (cx, cy)) in enumerate(zip(ODDTEX, ODDTEX_UV, ODDTEX_CENTRES)):
+        px = oddtex_texels(k)
+        path = os.path.join(d, "t%d.png" % k)
+        if c == 3:
+            argb = (np.uint32(255) << 24) | (px[:, :, 0].astype(np.uint32) << 16) | (px[:, :, 1].astype(np.uint32) << 8) | px[:, :, 2]
+            ap = os.path.join(tmp, "t%d.argb" % k)
+            argb.astype(np.uint32).tofile(ap)
+            run(["savepng", ap, w, h, path])
+        else:
+            Image.fromarray(px, "RGBA").save(path, optimize=False)
+        assert (np.asarray(Image.open(path)) == px).all()
+        corners = [(cx - 0.9, cy - 0.9, u0, v0), (cx + 0.9, cy - 0.9, u1, v0), (cx + 0.9, cy + 0.9, u1, v1), (cx - 0.9, cy + 0.9, u0, v1)]
+        for x, y, u, v in corners:
+            obj.append("v %g %g %g" % (x, y, 0.15 * x + 0.1 * y))
+        for x, y, u, v in corners:
+            obj.append("vt %g %g" % (u, v))
+        obj.append("usemtl m%d" % k)
+        obj.append("f " + " ".join("%d/%d/1" % (4 * k + i + 1, 4 * k + i + 1) for i in range(4)))
+        mtl += ["newmtl m%d" % k, "map_Kd t%d.png" % k, ""]
+    open(os.path.join(d, "oddtex.obj"), "w").write("\n".join(obj) + "\n")
+    open(os.path.join(d, "oddtex.mtl"), "w").write("\n".join(mtl))
+    rng = np.random.default_rng(20261022)
+    fed = O.Scene()
+    sh = fed.add_mesh_obj(os.path.join(d, "oddtex.obj"), load_textures=False)
+    for k in range(len(ODDTEX)):
+        uv = oddtex_uv(k, rng)
+        up, op = os.path.join(tmp, "uv.bin"), os.path.join(tmp, "tex.bin")
+        uv.tofile(up)
+        run(["texsample", os.path.join(d, "oddtex.obj"), k, up, len(uv), op])
+        rgba = np.fromfile(op, np.float32).reshape(-1, 4)
+        fed.set_texture(sh, k, oddtex_texels(k))        # the reference's loader read what was written: its samples are those of the texel array
+        assert (fed.texture_sample(sh, k, uv).view(np.uint32) == rgba.view(np.uint32)).all(), k
+        np.savez_compressed(os.path.join(OUT, "texsample_oddtex_m%d.npz" % k), uv=uv, material=np.int32(k), rgba=rgba)
+
+
 def golden_scene_frame(name, tag, W, Hh, ns, depth, preview, seed, pass0, npass, tmp):
     sp, fp = write_scene_file(SC.SCENES[tag](), tmp, tag), os.path.join(tmp, "frame")
     run(["frame", sp, "-", W, Hh, ns, depth, preview, seed, pass0, npass, 0, W * Hh - 1, fp])
@@ -260,6 +559,11 @@ def main():
         with tempfile.TemporaryDirectory() as tmp:
             golden_misc(tmp)
         return
+    if "--edges-only" in sys.argv:         # add the edge-case fixtures (tests/test_edges_*.py) without regenerating the others
+        with tempfile.TemporaryDirectory() as tmp:
+            golden_edges(tmp)
+            golden_oddtex(tmp)
+        return
     if "--scenes-only" in sys.argv:        # add the multi-shape fixtures without regenerating the others
         rng = np.random.default_rng(20261005)
         with tempfile.TemporaryDirectory() as tmp:
@@ -293,6 +597,8 @@ def main():
         main_scenes(tmp, np.random.default_rng(20261005), bounds)
         main_worker(tmp)
         golden_misc(tmp)
+        golden_edges(tmp)
+        golden_oddtex(tmp)
     total = sum(os.path.getsize(os.path.join(OUT, f)) for f in os.listdir(OUT) if f.endswith(".npz"))
     print("golden fixtures written: %.2f MB" % (total / 1e6))
 

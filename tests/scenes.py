@@ -118,8 +118,32 @@ def tris_scene():
     ]
 
 
+def edges_scene(negative=False):
+    """Analytic shapes with parameters chosen for trouble (tests/golden/make_golden.py:make_edge_rays aims at their tangents, surfaces,
+    segment ends, seams and axes), an untextured mesh in the middle of the list.  Materials without Blend or fuzziness, so a moved camera
+    can be followed by the oracle (tests/camera_support.py).  negative=True appends a sphere of negative radius: the reference stops at
+    an assertion on that shape's inverted box (Src/RRay.cpp:91), so no fixture holds it; the oracle and the device are compared on it."""
+    return [
+        ("sphere", (-4.0, 3.0, 0.0), 1e-4, emissive((2.0, 0.5, 0.5))),                                  # 0: tiny
+        ("sphere", (-2.0, 3.0, 0.0), 0.0, diffuse((1, 1, 1))),                                          # 1: radius 0
+        ("sphere", (0.0, -10006.0, 0.0), 1e4, checker((0.7, 0.8, 0.9), 2.0)),                           # 2: huge, its top at y = -6
+        ("sphere", (3000.0, -2000.0, 1000.0), 1.0, diffuse((0.2, 0.9, 0.3))),                           # 3: far from the origin: the quadratic's constant term cancels
+        ("sphere", (2.0, 3.0, 0.0), 0.5, diffuse((0.3, 0.3, 0.9))),                                     # 4: coincident with 6: which of the two is reported hangs on a last bit
+        ("mesh", "TorusKnot", reflective((0.9, 0.9, 0.9))),                                             # 5
+        ("sphere", (2.0, 3.0, 0.0), 0.5, combine(diffuse((0.9, 0.8, 0.2)), emissive((0.1, 0.1, 0.3)))),  # 6
+        ("plane", (0.0, 2.0, 0.0), (0.0, -5.0, 0.0), checker((0.9, 0.9, 0.9), 1.5)),                    # 7: non-unit normal
+        ("plane", (0.0, 0.0, 0.0), (0.0, 0.0, 0.0), diffuse((1, 0, 0))),                                # 8: zero normal, never hit
+        ("capsule", (-4.0, -2.0, 0.0), (-2.0, -2.0, 0.0), 0.5, reflective((0.8, 0.9, 0.8))),            # 9: along x
+        ("capsule", (4.0, -3.0, 1.0), (4.0, -1.0, 1.0), 0.3, diffuse((0.9, 0.5, 0.1))),                 # 10: along y
+        ("capsule", (0.0, -3.0, 2.0), (0.0, -3.0, 2.0), 0.4, diffuse((0.4, 0.9, 0.9))),                 # 11: Start == End
+        ("capsule", (2.0, -3.0, 2.0), (2.0, -3.0, 2.00001), 0.4, diffuse((0.9, 0.4, 0.9))),             # 12: length 1e-5
+        ("capsule", (-25.0, 5.0, -3.0), (25.0, 5.0, -3.0), 1e-3, emissive((1.0, 1.0, 4.0))),            # 13: long and thin
+        ("triangle", (-4.0, 0.0, 1.0), (-2.5, 0.2, 1.3), (-3.2, 1.5, 0.8), diffuse((0.9, 0.9, 0.4))),   # 14
+    ] + ([("sphere", (0.0, 3.0, 0.0), -0.5, diffuse((0.9, 0.3, 0.3)))] if negative else [])            # 15: only the radius's square and the box use it
+
+
 SCENES = {"tris": tris_scene, "room": room_scene, "default": lambda: default_scene(True), "default_nofuzz": lambda: default_scene(False),
-          "quirk": quirk_scene, "shapes": shapes_scene}
+          "quirk": quirk_scene, "shapes": shapes_scene, "edges": edges_scene, "edges_negative": lambda: edges_scene(True)}
 
 
 def scene_bounds(scene, mesh_bounds):

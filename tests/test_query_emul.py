@@ -31,7 +31,7 @@ def scene_text(shapes):
 # rays a job keeps of its fixture, spread evenly over it.  The stand-in runs a few hundred rays a second, so two jobs -- unitychan (a tree larger
 # than the staged part, textures) and the texel-inheritance scene (analytic shapes) -- are long enough for a second trip of a wave through the batch
 # loop (1100 rays = 18 batches on the 16 waves of ONE block, the last batch 12 rays, on a second trip); the GPU suite runs the full fixtures.
-KEEP = {"torus_p0": 130, "torus_p1": 130, "unity": 1100, "quirk": 1100, "default_nofuzz": 130}
+KEEP = {"torus_p0": 130, "torus_p1": 130, "unity": 1100, "quirk": 1100, "default_nofuzz": 130, "edges": 260}
 
 
 def spread(idx, count):
@@ -51,6 +51,16 @@ def base_jobs():
     for tag in ("quirk", "default_nofuzz"):
         g = np.load(os.path.join(GOLDEN, "sceneclosest_%s.npz" % tag))
         jobs[tag] = (scene_text(SC.SCENES[tag]()), g, spread(np.arange(len(g["rays"])), KEEP[tag]), 1)
+    # the rays aimed at the analytic shapes' edges (tests/golden/make_golden.py:make_edge_rays): every family's share of the 260, at least 4 of each,
+    # spread evenly over the family (so over its shapes).  Rays whose reference record holds a NaN (a NaN's sign and payload are not specified, and
+    # the comparison below is on bits) stay with tests/test_edges_cpu.py and the GPU suite, which compare them by the NaN rule.
+    g = np.load(os.path.join(GOLDEN, "sceneclosest_edges.npz"))
+    usable = ~((g["shape"] >= 0) & np.isnan(g["hit"]).any(axis=1))
+    keep = []
+    for f in np.unique(g["family"]):
+        idx = np.flatnonzero((g["family"] == f) & usable)
+        keep.append(spread(idx, min(len(idx), max(4, round(KEEP["edges"] * len(idx) / len(usable))))))
+    jobs["edges"] = (scene_text(SC.SCENES["edges"]()), g, np.unique(np.concatenate(keep)), 1)
     return jobs
 
 
@@ -59,7 +69,7 @@ def runs_of(base):
     return r + [(base, None, 0, 1, 1), (base, None, 3, 1, 2), (base, None, 1, 1, 3)]        # tri NULL; only shape; shape and tri without hits
 
 
-BASES = ("torus_p0", "torus_p1", "unity", "quirk", "default_nofuzz")
+BASES = ("torus_p0", "torus_p1", "unity", "quirk", "default_nofuzz", "edges")
 RUNS = [r for b in BASES for r in runs_of(b)]
 
 
@@ -91,7 +101,8 @@ def dumps(tmp_path_factory):
     return out, report, jobs
 
 
-TIMEOUT = 1200      # twice the program's measured run on the CPU (600 s with the build, beside other work on the machine)
+TIMEOUT = 1226      # twice the program's measured run on the CPU (600 s with the build, beside other work on the machine), plus twice the edges job's
+                    # (its 33 runs alone: 13 s; the whole module with it, the program already built: 517 s)
 
 
 def bits(a):
