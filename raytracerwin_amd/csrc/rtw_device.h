@@ -19,42 +19,44 @@ inline size_t level_workspace_bytes(long long work_items, int max_bounce)
 struct PipelineLayout { size_t queue_off, pend_off, counters_off, rad_off, hit_off, state_off, tlist0_off, tlist1_off, ws_off, total, capacity; };
 // workspace of the bins + wave pipeline (pipeline 3) for a launch of `work_items` pixels (device bytes)
 size_t pipeline_workspace_bytes(long long work_items, int max_bounce, PipelineLayout* out);
-struct PipelineTuning {
-    int expected_paths;    // queue length seen by the previous pass on this context, -1 = unknown
-    int round_hint[32];    // trace-list lengths of the previous pass per round, -1 = unknown
-    // jobs [sky_job0, n_jobs) of the job table are sky-only tiles, rendered by primary_sky_kernel on aux_stream
-    // between the two events (fork after the previous work of the main stream, join before the pass ends); aux_stream null = one kernel
-    hipStream_t aux_stream; hipEvent_t fork_event, join_event; int sky_job0; const float* gamma_thr;
-    bool has_analytic = false;  // some shape is a sphere / plane / capsule: the kernels' instantiations that hold those tests are launched
-    // a run of passes inside one rtw_render_passes call forks the second stream before its first pass and joins it after its last:
-    // between those passes nothing else can be enqueued, the sky kernels are ordered on their own stream and write pixels no other
-    // kernel of the run writes
+// Sky-only tiles are rendered by a kernel of their own on aux_stream, between the two events (fork after the previous work of the main stream, join
+// before the pass or group ends); aux_stream null = on the main stream.  A run of passes inside one rtw_render_passes call forks the second stream before
+// its first pass and joins it after its last: between those passes nothing else can be enqueued, the sky kernels are ordered on their own stream and
+// write pixels no other kernel of the run writes.
+struct AuxFork {
+    hipStream_t aux_stream = nullptr; hipEvent_t fork_event = nullptr, join_event = nullptr;
     bool do_fork = true, do_join = true;
     bool* aux_unjoined = nullptr;   // set when a sky kernel was launched and the join was left to a later pass
+};
+struct PipelineTuning : AuxFork {
+    int expected_paths;    // queue length seen by the previous pass on this context, -1 = unknown
+    int round_hint[32];    // trace-list lengths of the previous pass per round, -1 = unknown
+    int sky_job0; const float* gamma_thr;   // jobs [sky_job0, n_jobs) of the job table are sky-only tiles, rendered by primary_sky_kernel
+    bool has_analytic = false;  // some shape is a sphere / plane / capsule: the kernels' instantiations that hold those tests are launched
     bool skip_trace = false;    // every shape is a leading analytic shape: the shading lanes do the whole scene query, no trace launches
     bool counters_clean;   // the counters are known to be zero (left so by the previous pass): no memset
     int cu_count;
     hipEvent_t* timing;    // null, or 4 events recorded before the primary kernel and after each of the three stages
 };
 int launch_render_pipeline(const RtwSceneDev* sc, void* accum, void* argb, void* workspace, const RtwRenderParams& p, const PipelineTuning& tune, bool stats, hipStream_t stream);
-// device address of the pipeline's counters inside the workspace (for the asynchronous read-back of the queue length)
-size_t pipeline_counters_offset(long long work_items, int max_bounce);
 // ---- pass-batched pipeline (pipeline 4, rtw_group_kernels.h) ----
 // slots of a group's workspace (rtw_group_kernels.h group_slot): one per path and pass
 inline size_t group_capacity(size_t paths_per_pass, int n_passes) { return paths_per_pass * (size_t)(n_passes > 0 ? n_passes : 1); }
 struct GroupLayout { size_t counters_off, rad_off, state_off, hit_off, carry_off, levels_off, list0_off, list1_off, overflow_off, tlist0_off, tlist1_off, total; };
 // device bytes of a group's workspace: `capacity` path slots (busy tiles x 64 x sub-samples x passes of the group, rounded up to a power of two of passes)
 size_t group_workspace_bytes(size_t capacity, int max_bounce, bool carry, GroupLayout* out);
-struct GroupTuning {
+struct GroupTuning : AuxFork {      // (the sky-only tiles run on aux_stream beside the rest of the group)
     size_t capacity = 0;
-    hipStream_t aux_stream = nullptr; hipEvent_t fork_event = nullptr, join_event = nullptr;   // sky-only tiles run on aux_stream beside the rest of the group
-    bool do_fork = true, do_join = true; bool* aux_unjoined = nullptr;
     const float* gamma_thr = nullptr;
     bool has_analytic = false;     // some shape is a sphere / plane / capsule / triangle
     bool carry = false;            // ... and one of them follows a textured mesh: hit records carry the mesh hit whose texel the hit keeps
     bool counters_clean = false;   // the list counters are zero (left so by the previous group)
     int round_hint[32];            // list lengths of the previous group per round (-1 = unknown): they size the launches
     int cu_count = 256;
+    int staged_shape = -1, staged_top = 0;   // the trace blocks stage the first staged_top tnodes records of this shape in LDS (-1: nothing staged)
+    bool staged_all = false;                 // ... and that is the shape's whole tree
+    bool staged_planes = false;              // ... and the triangles' planes are staged beside it (persistent kernel: back-facing leaves are never noted)
+    int staged_tris = 0;                     // triangles of the staged shape
     bool single_mesh = false;      // the scene is one mesh: the trace rounds run persistent waves that refill their lanes
     bool lead_mesh = false;        // ... or leading analytic shapes followed by ONE mesh (shape staged_shape), no texel inheritance: the same kernel, continuing the lead query
     // a group rendered as several parts on as many streams (rtwin_capi.cpp: rtw_render_passes): the group's sky tiles are rendered for ALL its passes
@@ -67,10 +69,6 @@ struct GroupTuning {
     bool skip_trace = false;                 // every shape is a leading analytic shape: the shading lanes do the whole query, no trace launches
     int overflow_hint[32];                   // how many rays that were in the previous group, per round (-1 = unknown)
     int wave_below = 0;                      // a trace round whose list (previous group's length) is shorter than this runs a wave per ray
-    bool staged_all = false;                 // ... and that is the shape's whole tree
-    int staged_tris = 0;                     // triangles of the staged shape
-    bool staged_planes = false;              // ... and the triangles' planes are staged beside it (persistent kernel: back-facing leaves are never noted)
-    int staged_shape = -1, staged_top = 0;   // the trace blocks stage the first staged_top tnodes records of this shape in LDS (-1: nothing staged)
     hipEvent_t* timing = nullptr;  // null, or 4 events: before the primary kernel, after it, after the bounce rounds, after resolve
 };
 int launch_render_group(const RtwSceneDev* sc, void* accum, void* argb, void* workspace, const RtwGroupParams& g, const GroupTuning& tune, bool stats, hipStream_t stream);

@@ -13,6 +13,8 @@
 #include <string.h>
 #include <vector>
 #include <cstring>
+#include <algorithm>
+#include <type_traits>
 
 #include "rtw_types.h"
 #include "rtw_device.h"
@@ -1252,6 +1254,66 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(GatherPlan g)
     }
 }
 
+// ---- how a launch picks its instantiation ---------------------------------------------------------------------
+// A runtime flag handed to a generic lambda as std::true_type / std::false_type: the lambda names the kernel once, with decltype(FLAG)::value as
+// template arguments, and exactly the combinations of flags a call site passes are instantiated.
+template <typename F> void with_flags(bool a, F&& f) { if (a) f(std::true_type{}); else f(std::false_type{}); }
+template <typename F> void with_flags(bool a, bool b, F&& f) { with_flags(a, [&](auto A) { with_flags(b, [&](auto B) { f(A, B); }); }); }
+template <typename F> void with_flags(bool a, bool b, bool c, F&& f) { with_flags(a, [&](auto A) { with_flags(b, c, [&](auto B, auto C) { f(A, B, C); }); }); }
+// The three block shapes of the ray-per-lane trace kernels (gtrace_kernel, qtrace_kernel): 1024 threads with a tree's upper levels staged in LDS
+// (STG 1) or its whole tree (STG 2), 256 threads with nothing staged (STG 0).  lds(top): candidate lists + `top` staged records.
+template <int NT_, int CAP_, int STG_> struct TraceShape {
+    static constexpr int NT = NT_, CAP = CAP_, STG = STG_;
+    static size_t lds(int top) { return (size_t)CAP * NT * 4 + (STG ? (size_t)top * 32 : 0); }
+};
+template <typename F> void with_trace_shape(bool staged, bool staged_all, F&& f)
+{
+    if (!staged) f(TraceShape<256, RTW_GT_CAP, 0>{});
+    else if (staged_all) f(TraceShape<1024, RTW_GT_CAP_STAGED, 2>{});
+    else f(TraceShape<1024, RTW_GT_CAP_STAGED, 1>{});
+}
+// Every launch: more than 64 KiB of dynamic LDS has to be allowed for the instantiation first.
+template <typename... P, typename... A>
+void launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t dyn_lds, hipStream_t stream, const A&... args)
+{
+    if (dyn_lds > 65536) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_lds);
+    hipLaunchKernelGGL(kernel, grid, block, dyn_lds, stream, static_cast<P>(args)...);
+}
+
+// ---- launch sizes from the previous pass's / group's list lengths -------------------------------------------------
+// The true length of a list is only known on the device; the host sizes a launch by the length the list had last time (`hint`, -1 = unknown: `most`)
+// plus a quarter plus `margin`, at most `most`.  Any shortfall is absorbed by stride loops, any excess by blocks that exit at once.
+long long items_from_hint(long long hint, int margin, long long most)
+{
+    if (hint < 0) return most;
+    const long long want = hint + hint / 4 + margin;
+    return want < most ? want : most;
+}
+unsigned blocks_of(long long items, int lanes, long long cap)       // blocks of `lanes` items each, between 1 and `cap`
+{
+    const long long b = (items + lanes - 1) / lanes;
+    return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
+}
+unsigned blocks_from_hint(long long hint, int margin, int lanes, long long cap, long long most) { return blocks_of(items_from_hint(hint, margin, most), lanes, cap); }
+
+// ---- the sky-only tiles on the second stream, beside the rest of a pass or group (rtw::AuxFork) -------------------------
+// Fork aux_stream off `stream` (unless an earlier pass of the run has), run launch_sky(aux_stream), then record the join event or leave the join to a
+// later pass of the run.  False: the fork failed and nothing was launched.
+template <typename F> bool fork_sky(const rtw::AuxFork& t, hipStream_t stream, F&& launch_sky)
+{
+    if (t.do_fork && !(hipEventRecord(t.fork_event, stream) == hipSuccess && hipStreamWaitEvent(t.aux_stream, t.fork_event, 0) == hipSuccess)) return false;
+    launch_sky(t.aux_stream);
+    if (t.do_join) (void)hipEventRecord(t.join_event, t.aux_stream);
+    else if (t.aux_unjoined) *t.aux_unjoined = true;
+    return true;
+}
+void join_sky(const rtw::AuxFork& t, bool forked, hipStream_t stream)      // the pass (or the run of passes) is complete when both streams are
+{
+    if (!forked || !t.do_join) return;
+    (void)hipStreamWaitEvent(stream, t.join_event, 0);
+    if (t.aux_unjoined) *t.aux_unjoined = false;
+}
+
 }  // namespace
 
 // ---- launch wrappers ---------------------------------------------------------------------------------------
@@ -1262,13 +1324,9 @@ int launch_render(const RtwSceneDev* sc, void* accum, void* argb, void* ws, cons
     if (p.count <= 0) return 0;
     const int block = 256;
     const int grid = (p.count + block - 1) / block;
-    if (p.cam_general) {
-        if (stats) hipLaunchKernelGGL((render_kernel<true, true>), dim3(grid), dim3(block), 0, stream, sc, (float4*)accum, (uint32_t*)argb, (float4*)ws, p);
-        else hipLaunchKernelGGL((render_kernel<false, true>), dim3(grid), dim3(block), 0, stream, sc, (float4*)accum, (uint32_t*)argb, (float4*)ws, p);
-    } else {
-        if (stats) hipLaunchKernelGGL((render_kernel<true, false>), dim3(grid), dim3(block), 0, stream, sc, (float4*)accum, (uint32_t*)argb, (float4*)ws, p);
-        else hipLaunchKernelGGL((render_kernel<false, false>), dim3(grid), dim3(block), 0, stream, sc, (float4*)accum, (uint32_t*)argb, (float4*)ws, p);
-    }
+    with_flags(stats, p.cam_general != 0, [&](auto ST, auto CAM) {
+        launch(render_kernel<decltype(ST)::value, decltype(CAM)::value>, dim3(grid), dim3(block), 0, stream, sc, (float4*)accum, (uint32_t*)argb, (float4*)ws, p);
+    });
     return (int)hipGetLastError();
 }
 
@@ -1293,13 +1351,6 @@ size_t pipeline_workspace_bytes(long long work_items, int max_bounce, PipelineLa
     return l.total;
 }
 
-size_t pipeline_counters_offset(long long work_items, int max_bounce)
-{
-    PipelineLayout l;
-    pipeline_workspace_bytes(work_items, max_bounce, &l);
-    return l.counters_off;
-}
-
 // One pass through the bins + wave pipeline: primary_bins_kernel (+ primary_sky_kernel on the second stream), then trace(r - 1) / shade(r) for
 // r = 1 .. max_bounce - 1 (the primary kernel was shade(0)), then resolve_kernel.
 int launch_render_pipeline(const RtwSceneDev* sc, void* accum, void* argb, void* workspace, const RtwRenderParams& p, const PipelineTuning& tune, bool stats, hipStream_t stream)
@@ -1315,102 +1366,60 @@ int launch_render_pipeline(const RtwSceneDev* sc, void* accum, void* argb, void*
     hipError_t e = hipSuccess;
     if (!tune.counters_clean) e = hipMemsetAsync(pb.counters, 0, 256, stream);     // else: the previous pass's resolve_kernel left them zeroed
     if (e != hipSuccess) return (int)e;
-    // Paths to size the launches for.  The true queue length is only known on the device; the host passes the length the previous pass had
-    // (frames of a progressive render barely differ) plus a margin.  Any shortfall is absorbed by stride loops, any excess by blocks that exit at once.
-    long long owners = (long long)l.capacity;
-    if (tune.expected_paths >= 0) {
-        const long long want = (long long)tune.expected_paths + tune.expected_paths / 4 + 1024;
-        if (want < owners) owners = want;
-    }
+    // Paths to size the launches for: the queue length the previous pass had (frames of a progressive render barely differ) plus a margin.
+    const long long owners = items_from_hint(tune.expected_paths, 1024, (long long)l.capacity);
     const int block = 256;
     const int grid = (p.count + block - 1) / block;
-    int resolve_blocks = grid < 1024 ? grid : 1024;
-    if (tune.expected_paths >= 0) {      // a thread per pending pixel (at most one per queued path), not per pixel of the frame
-        const int want = (tune.expected_paths + tune.expected_paths / 4 + 1024 + 255) / 256;
-        if (want < resolve_blocks) resolve_blocks = want;
-    }
+    // resolve: a thread per pending pixel (at most one per queued path), not per pixel of the frame
+    const unsigned resolve_blocks = blocks_from_hint(tune.expected_paths, 1024, 256, grid < 1024 ? grid : 1024, p.count);
     if (tune.timing) (void)hipEventRecord(tune.timing[0], stream);
     bool forked = false;
     {
         RtwRenderParams ph = p;
         if (tune.aux_stream && p.tile_order && tune.sky_job0 > 0 && tune.sky_job0 < p.n_jobs && !stats) {
             // sky-only tiles on the second stream, beside everything else of this pass
-            forked = !tune.do_fork || (hipEventRecord(tune.fork_event, stream) == hipSuccess && hipStreamWaitEvent(tune.aux_stream, tune.fork_event, 0) == hipSuccess);
-            if (forked) {
+            forked = fork_sky(tune, stream, [&](hipStream_t ss) {
                 const int sky_jobs = p.n_jobs - tune.sky_job0;
                 int sgrid = (sky_jobs + 3) / 4;
                 if (sgrid > tune.cu_count * 64) sgrid = tune.cu_count * 64;
-                if (p.cam_general) hipLaunchKernelGGL(primary_sky_kernel<true>, dim3(sgrid), dim3(block), 0, tune.aux_stream, tune.gamma_thr, (float4*)accum, (uint32_t*)argb, p, tune.sky_job0);
-                else hipLaunchKernelGGL(primary_sky_kernel<false>, dim3(sgrid), dim3(block), 0, tune.aux_stream, tune.gamma_thr, (float4*)accum, (uint32_t*)argb, p, tune.sky_job0);
-                if (tune.do_join) (void)hipEventRecord(tune.join_event, tune.aux_stream);
-                else if (tune.aux_unjoined) *tune.aux_unjoined = true;
-                ph.n_jobs = tune.sky_job0;
-            }
+                with_flags(p.cam_general != 0, [&](auto CAM) {     // (the general-camera instantiation; the default pose keeps the fixed-pose one)
+                    launch(primary_sky_kernel<decltype(CAM)::value>, dim3(sgrid), dim3(block), 0, ss, tune.gamma_thr, (float4*)accum, (uint32_t*)argb, p, tune.sky_job0);
+                });
+            });
+            if (forked) ph.n_jobs = tune.sky_job0;
         }
         const int jobs_grid = ph.tile_order ? (ph.n_jobs + 3) / 4 : grid;        // a wave per job (a tile, or a tile's sub-sample); else waves take jobs in turn
         const int pgrid = jobs_grid < tune.cu_count * 64 ? jobs_grid : tune.cu_count * 64;
-        // (CAM_: the general-camera instantiation; the default pose keeps the fixed-pose one)
-#define RTW_PRIMARY_BINS(CAM_) do { \
-        if (tune.has_analytic) { \
-            if (stats) hipLaunchKernelGGL((primary_bins_kernel<true, true, CAM_>), dim3(pgrid), dim3(block), 0, stream, sc, (float4*)accum, (uint32_t*)argb, pb, ph); \
-            else hipLaunchKernelGGL((primary_bins_kernel<false, true, CAM_>), dim3(pgrid), dim3(block), 0, stream, sc, (float4*)accum, (uint32_t*)argb, pb, ph); \
-        } else { \
-            if (stats) hipLaunchKernelGGL((primary_bins_kernel<true, false, CAM_>), dim3(pgrid), dim3(block), 0, stream, sc, (float4*)accum, (uint32_t*)argb, pb, ph); \
-            else hipLaunchKernelGGL((primary_bins_kernel<false, false, CAM_>), dim3(pgrid), dim3(block), 0, stream, sc, (float4*)accum, (uint32_t*)argb, pb, ph); \
-        } } while (0)
-        if (p.cam_general) RTW_PRIMARY_BINS(true); else RTW_PRIMARY_BINS(false);
-#undef RTW_PRIMARY_BINS
+        with_flags(stats, tune.has_analytic, p.cam_general != 0, [&](auto ST, auto AN, auto CAM) {
+            launch(primary_bins_kernel<decltype(ST)::value, decltype(AN)::value, decltype(CAM)::value>, dim3(pgrid), dim3(block), 0, stream, sc, (float4*)accum, (uint32_t*)argb, pb, ph);
+        });
     }
     if (tune.timing) (void)hipEventRecord(tune.timing[1], stream);
-    auto items_of = [&](int round) {
-        if (round <= 1) return owners;      // the queue is round 0's trace list = round 1's input
-        const long long items = tune.round_hint[round - 1] >= 0 ? (long long)tune.round_hint[round - 1] + tune.round_hint[round - 1] / 4 + 256 : owners;
-        return items > owners ? owners : items;
-    };
+    auto hint_of = [&](int round) { return round <= 1 ? -1 : tune.round_hint[round - 1]; };      // the queue is round 0's trace list = round 1's input: `owners`
     constexpr int NTV = 128;                // wave-per-ray trace launches: 128-thread blocks (measured a little faster than 256: fewer waves coupled to one block)
     const size_t dyn = (size_t)(NTV / 64) * RTW_WAVE_LDS_WORDS * 4;
     const long long trace_cap = (long long)tune.cu_count * (1024 / NTV) * 8;
     for (int r = 1; r < p.max_bounce; r++) {
-        if (!tune.skip_trace) {
-            const long long rays = items_of(r);
-            if (p.lead_shapes > 0) {        // leading analytic shapes: the records are half done, most rays need no trace (see trace_wave_lead_kernel)
-                int shift = 0;              // measured on SetupScene: 4 entries per wave at a time 1.64 ms, 16: 1.67, 64: 1.84, 1: 1.80 (flagged rays cluster: small chunks spread them over the waves)
-                while (shift < 2 && (rays >> (shift + 1)) >= 16384) shift++;
-                long long blocks = ((rays >> shift) + NTV / 64) / (NTV / 64);
-                if (blocks < 1) blocks = 1;
-                if (blocks > trace_cap) blocks = trace_cap;
-                if (stats) hipLaunchKernelGGL((trace_wave_lead_kernel<true, NTV>), dim3((unsigned)blocks), dim3(NTV), dyn, stream, sc, pb, p, r - 1, shift);
-                else hipLaunchKernelGGL((trace_wave_lead_kernel<false, NTV>), dim3((unsigned)blocks), dim3(NTV), dyn, stream, sc, pb, p, r - 1, shift);
-            } else {
-                long long blocks = (rays + NTV / 64 - 1) / (NTV / 64);
-                if (blocks < 1) blocks = 1;
-                if (blocks > trace_cap) blocks = trace_cap;
-                if (tune.has_analytic) {    // analytic shapes somewhere after a mesh: the general wave-per-ray query
-                    if (stats) hipLaunchKernelGGL((trace_wave_kernel<true, NTV, true>), dim3((unsigned)blocks), dim3(NTV), dyn, stream, sc, pb, p, r - 1);
-                    else hipLaunchKernelGGL((trace_wave_kernel<false, NTV, true>), dim3((unsigned)blocks), dim3(NTV), dyn, stream, sc, pb, p, r - 1);
-                } else {
-                    if (stats) hipLaunchKernelGGL((trace_wave_kernel<true, NTV, false>), dim3((unsigned)blocks), dim3(NTV), dyn, stream, sc, pb, p, r - 1);
-                    else hipLaunchKernelGGL((trace_wave_kernel<false, NTV, false>), dim3((unsigned)blocks), dim3(NTV), dyn, stream, sc, pb, p, r - 1);
-                }
-            }
+        if (tune.skip_trace) {              // every shape is a leading shape: nothing is left for a trace launch
+        } else if (p.lead_shapes > 0) {     // leading analytic shapes: the records are half done, most rays need no trace (see trace_wave_lead_kernel)
+            const long long rays = items_from_hint(hint_of(r), 256, owners);
+            int shift = 0;                  // measured on SetupScene: 4 entries per wave at a time 1.64 ms, 16: 1.67, 64: 1.84, 1: 1.80 (flagged rays cluster: small chunks spread them over the waves)
+            while (shift < 2 && (rays >> (shift + 1)) >= 16384) shift++;
+            with_flags(stats, [&](auto ST) {
+                launch(trace_wave_lead_kernel<decltype(ST)::value, NTV>, dim3(blocks_of((rays >> shift) + 1, NTV / 64, trace_cap)), dim3(NTV), dyn, stream, sc, pb, p, r - 1, shift);
+            });
+        } else {                            // (has_analytic: analytic shapes somewhere after a mesh, the general wave-per-ray query)
+            with_flags(stats, tune.has_analytic, [&](auto ST, auto AN) {
+                launch(trace_wave_kernel<decltype(ST)::value, NTV, decltype(AN)::value>, dim3(blocks_from_hint(hint_of(r), 256, NTV / 64, trace_cap, owners)), dim3(NTV), dyn, stream, sc, pb, p, r - 1);
+            });
         }
-        long long sb = (items_of(r) + 255) / 256;
-        if (sb < 1) sb = 1;
-        if (sb > 262144) sb = 262144;
-        if (tune.has_analytic) {
-            if (stats) hipLaunchKernelGGL((shade_kernel<true, true>), dim3((unsigned)sb), dim3(256), 0, stream, sc, pb, p, r);
-            else hipLaunchKernelGGL((shade_kernel<false, true>), dim3((unsigned)sb), dim3(256), 0, stream, sc, pb, p, r);
-        } else {
-            if (stats) hipLaunchKernelGGL((shade_kernel<true, false>), dim3((unsigned)sb), dim3(256), 0, stream, sc, pb, p, r);
-            else hipLaunchKernelGGL((shade_kernel<false, false>), dim3((unsigned)sb), dim3(256), 0, stream, sc, pb, p, r);
-        }
+        with_flags(stats, tune.has_analytic, [&](auto ST, auto AN) {
+            launch(shade_kernel<decltype(ST)::value, decltype(AN)::value>, dim3(blocks_from_hint(hint_of(r), 256, 256, 262144, owners)), dim3(256), 0, stream, sc, pb, p, r);
+        });
     }
     if (tune.timing) (void)hipEventRecord(tune.timing[2], stream);
-    hipLaunchKernelGGL(resolve_kernel, dim3(resolve_blocks), dim3(block), 0, stream, sc, (float4*)accum, (uint32_t*)argb, pb, p);
-    if (forked && tune.do_join) {           // the pass (or the run of passes) is complete when both streams are
-        (void)hipStreamWaitEvent(stream, tune.join_event, 0);
-        if (tune.aux_unjoined) *tune.aux_unjoined = false;
-    }
+    launch(resolve_kernel, dim3(resolve_blocks), dim3(block), 0, stream, sc, (float4*)accum, (uint32_t*)argb, pb, p);
+    join_sky(tune, forked, stream);
     if (tune.timing) (void)hipEventRecord(tune.timing[3], stream);
     return (int)hipGetLastError();
 }
@@ -1441,14 +1450,16 @@ int launch_render_group(const RtwSceneDev* sc, void* accum, void* argb, void* wo
 {
     const RtwRenderParams& p = g.rp;
     if (g.n_passes <= 0 || (g.n_busy <= 0 && g.n_sky <= 0)) return 0;
+    auto launch_sky = [&](const RtwGroupParams& gs, hipStream_t ss) {
+        int sgrid = (gs.n_sky + 3) / 4;
+        if (sgrid > tune.cu_count * tune.sky_blocks) sgrid = tune.cu_count * tune.sky_blocks;
+        with_flags(p.cam_general != 0, [&](auto CAM) { launch(gsky_kernel<decltype(CAM)::value>, dim3(sgrid), dim3(256), 0, ss, tune.gamma_thr, (float4*)accum, (uint32_t*)argb, gs); });
+    };
     if (tune.sky_mode == 2) {       // only the sky tiles of a split group, all the group's passes
         if (g.n_sky > 0) {
             RtwGroupParams gs = g;
             gs.first_pass = tune.sky_first_pass; gs.n_passes = tune.sky_passes;
-            int sgrid = (gs.n_sky + 3) / 4;
-            if (sgrid > tune.cu_count * tune.sky_blocks) sgrid = tune.cu_count * tune.sky_blocks;
-            if (p.cam_general) hipLaunchKernelGGL(gsky_kernel<true>, dim3(sgrid), dim3(256), 0, stream, tune.gamma_thr, (float4*)accum, (uint32_t*)argb, gs);
-            else hipLaunchKernelGGL(gsky_kernel<false>, dim3(sgrid), dim3(256), 0, stream, tune.gamma_thr, (float4*)accum, (uint32_t*)argb, gs);
+            launch_sky(gs, stream);
         }
         return (int)hipGetLastError();
     }
@@ -1462,23 +1473,9 @@ int launch_render_group(const RtwSceneDev* sc, void* accum, void* argb, void* wo
     gb.capacity = (uint32_t)tune.capacity; gb.carry_on = tune.carry ? 1 : 0;
     if (!tune.counters_clean) { hipError_t e = hipMemsetAsync(gb.counters, 0, 256, stream); if (e != hipSuccess) return (int)e; }
     bool forked = false;
-    if (tune.sky_mode == 1) {
-        // a part of a split group: the sky tiles are not its business
-    } else if (g.n_sky > 0) {
-        RtwGroupParams gs = g;
-        hipStream_t ss = stream;
-        if (tune.aux_stream) {
-            forked = !tune.do_fork || (hipEventRecord(tune.fork_event, stream) == hipSuccess && hipStreamWaitEvent(tune.aux_stream, tune.fork_event, 0) == hipSuccess);
-            if (forked) ss = tune.aux_stream;
-        }
-        int sgrid = (g.n_sky + 3) / 4;
-        if (sgrid > tune.cu_count * tune.sky_blocks) sgrid = tune.cu_count * tune.sky_blocks;
-        if (p.cam_general) hipLaunchKernelGGL(gsky_kernel<true>, dim3(sgrid), dim3(256), 0, ss, tune.gamma_thr, (float4*)accum, (uint32_t*)argb, gs);
-        else hipLaunchKernelGGL(gsky_kernel<false>, dim3(sgrid), dim3(256), 0, ss, tune.gamma_thr, (float4*)accum, (uint32_t*)argb, gs);
-        if (forked) {
-            if (tune.do_join) (void)hipEventRecord(tune.join_event, tune.aux_stream);
-            else if (tune.aux_unjoined) *tune.aux_unjoined = true;
-        }
+    if (tune.sky_mode != 1 && g.n_sky > 0) {        // (1: a part of a split group, the sky tiles are not its business)
+        forked = tune.aux_stream && fork_sky(tune, stream, [&](hipStream_t ss) { launch_sky(g, ss); });
+        if (!forked) launch_sky(g, stream);
     }
     if (tune.timing) (void)hipEventRecord(tune.timing[0], stream);
     if (g.n_busy > 0) {
@@ -1487,132 +1484,69 @@ int launch_render_group(const RtwSceneDev* sc, void* accum, void* argb, void* wo
             const int ppw = (g.primary_passes > 1 && g.primary_passes * p.sub_samples <= 4) ? g.primary_passes : 1;        // as the kernel reads it
             const long long waves = (long long)g.n_jobs * ((g.n_passes + ppw - 1) / ppw);
             const unsigned pgrid = (unsigned)((waves + 3) / 4);
-#define RTW_GPRIMARY(CAM_) do { \
-            if (tune.has_analytic) { \
-                if (stats) hipLaunchKernelGGL((gprimary_kernel<true, true, CAM_>), dim3(pgrid), dim3(256), 0, stream, sc, gb, g); \
-                else hipLaunchKernelGGL((gprimary_kernel<false, true, CAM_>), dim3(pgrid), dim3(256), 0, stream, sc, gb, g); \
-            } else { \
-                if (stats) hipLaunchKernelGGL((gprimary_kernel<true, false, CAM_>), dim3(pgrid), dim3(256), 0, stream, sc, gb, g); \
-                else hipLaunchKernelGGL((gprimary_kernel<false, false, CAM_>), dim3(pgrid), dim3(256), 0, stream, sc, gb, g); \
-            } } while (0)
-            if (p.cam_general) RTW_GPRIMARY(true); else RTW_GPRIMARY(false);
-#undef RTW_GPRIMARY
+            with_flags(stats, tune.has_analytic, p.cam_general != 0, [&](auto ST, auto AN, auto CAM) {
+                launch(gprimary_kernel<decltype(ST)::value, decltype(AN)::value, decltype(CAM)::value>, dim3(pgrid), dim3(256), 0, stream, sc, gb, g);
+            });
         }
         if (tune.timing) (void)hipEventRecord(tune.timing[1], stream);
-        auto blocks_for = [&](int list_round) {      // blocks of 256 lanes for the paths of list `list_round` (a grid-stride loop takes any excess)
-            long long items = live_paths;
-            if (tune.round_hint[list_round] >= 0) {
-                const long long want = (long long)tune.round_hint[list_round] + tune.round_hint[list_round] / 4 + 1024;
-                if (want < items) items = want;
+        constexpr int NTV = 128;            // wave-per-ray launches: 128-thread blocks, a wave takes rays in turn
+        const size_t wave_lds = (size_t)(NTV / 64) * RTW_WAVE_LDS_WORDS * 4;
+        const long long wave_cap = (long long)tune.cu_count * 64;
+        for (int r = 1; r < p.max_bounce && !p.preview; r++) {      // the primary kernel was shade(0); trace(r - 1) then shade(r)
+            // blocks of 256 lanes (a grid-stride loop takes any excess) for the round's whole list (the shade launch) ...
+            const unsigned sb_full = blocks_from_hint(tune.round_hint[r - 1], 1024, 256, 65536, live_paths);
+            // ... and for the rays the trace launch takes: the whole list, or (leading analytic shapes) the part the shading lanes could not finish
+            const int trace_hint = p.lead_shapes > 0 ? tune.trace_hint[r - 1] : tune.round_hint[r - 1];
+            const unsigned tb = std::min(sb_full, blocks_from_hint(trace_hint, 1024, 256, 65536, live_paths));
+            auto trace_wave = [&](bool an, unsigned blocks, int from_overflow) {
+                with_flags(stats, an, [&](auto ST, auto AN) {
+                    launch(gtrace_wave_kernel<decltype(ST)::value, decltype(AN)::value, NTV>, dim3(blocks), dim3(NTV), wave_lds, stream, sc, gb, r - 1, from_overflow, p.lead_shapes);
+                });
+            };
+            if (tune.skip_trace) {          // every shape is a leading shape: nothing is left for a trace launch
+            } else if (!tune.carry && trace_hint >= 0 && trace_hint < tune.wave_below) {
+                trace_wave(tune.has_analytic, blocks_from_hint(trace_hint, 64, NTV / 64, wave_cap, LLONG_MAX), 0);      // a short list: a wave per ray
+            } else if ((tune.single_mesh || tune.lead_mesh) && tune.staged_top > 0) {
+                // one mesh: persistent waves that refill their lanes (one block per CU when the tree's upper levels are staged)
+                const unsigned sbl = std::min((tb + 3) / 4, (unsigned)tune.cu_count);
+                const size_t dyn = (size_t)RTW_GT_CAP_STAGED * 1024 * 4 + (size_t)tune.staged_top * 32;
+                auto persist = [&](auto STG, auto PL, size_t lds) {
+                    with_flags(stats, tune.lead_mesh, [&](auto ST, auto LD) {
+                        launch(gtrace_persist_kernel<decltype(ST)::value, 1024, RTW_GT_CAP_STAGED, decltype(STG)::value, decltype(LD)::value, decltype(PL)::value>,
+                               dim3(sbl), dim3(1024), lds, stream, sc, gb, r - 1, tune.visit_budget, tune.staged_shape);
+                    });
+                };
+                using stage_top = std::integral_constant<int, 1>; using stage_all = std::integral_constant<int, 2>;
+                if (tune.staged_all && tune.staged_planes) persist(stage_all{}, std::true_type{}, dyn + (size_t)tune.staged_tris * 16);
+                else if (tune.staged_all) persist(stage_all{}, std::false_type{}, dyn);
+                else persist(stage_top{}, std::false_type{}, dyn);
+                if (tune.visit_budget < INT32_MAX) {        // the rays that ran out of budget: a wave each (lead_mesh: continuing the lead query, as the persistent kernel did)
+                    // a generous grid: the count varies from group to group, a wave-per-ray loop with too few waves is slow (measured: 0.9 ms for a few
+                    // thousand rays on 256 waves), blocks without a ray leave at once
+                    const long long want = tune.overflow_hint[r - 1] >= 0 ? (long long)tune.overflow_hint[r - 1] * 4 + 8192 : 16384;
+                    trace_wave(tune.lead_mesh, blocks_of(want, NTV / 64, wave_cap), 1);
+                }
+            } else {
+                with_trace_shape(tune.staged_shape >= 0 && tune.staged_top > 0, tune.staged_all, [&](auto SH) {
+                    using S = decltype(SH);
+                    with_flags(stats, tune.has_analytic, [&](auto ST, auto AN) {
+                        launch(gtrace_kernel<decltype(ST)::value, decltype(AN)::value, S::NT, S::CAP, S::STG>, dim3((tb + S::NT / 256 - 1) / (S::NT / 256)), dim3(S::NT),
+                               S::lds(tune.staged_top), stream, sc, gb, r - 1, tune.staged_shape, p.lead_shapes);
+                    });
+                });
             }
-            long long bl = (items + 255) / 256;
-            if (bl < 1) bl = 1;
-            if (bl > 65536) bl = 65536;
-            return (unsigned)bl;
-        };
-        if (!p.preview) {
-            for (int r = 1; r < p.max_bounce; r++) {       // the primary kernel was shade(0); trace(r - 1) then shade(r)
-                const unsigned sb_full = blocks_for(r - 1);  // the round's whole list (the shade launch)
-                // the rays the trace launch takes: the whole list, or (leading analytic shapes) the part the shading lanes could not finish
-                const int trace_hint = p.lead_shapes > 0 ? tune.trace_hint[r - 1] : tune.round_hint[r - 1];
-                unsigned tb = sb_full;
-                if (p.lead_shapes > 0 && trace_hint >= 0) { long long bl = ((long long)trace_hint + trace_hint / 4 + 1024 + 255) / 256; if (bl < (long long)tb) tb = (unsigned)(bl < 1 ? 1 : bl); }
-                if (!tune.skip_trace) {
-#define RTW_LAUNCH_GT(ST, AN_, NT_, CAP_, STG, BLOCKS, DYN)                                                                                      \
-                do {                                                                                                                            \
-                    if ((DYN) > 65536) (void)hipFuncSetAttribute((const void*)gtrace_kernel<ST, AN_, NT_, CAP_, STG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(DYN)); \
-                    hipLaunchKernelGGL((gtrace_kernel<ST, AN_, NT_, CAP_, STG>), dim3(BLOCKS), dim3(NT_), (DYN), stream, sc, gb, r - 1, tune.staged_shape, p.lead_shapes); \
-                } while (0)
-#define RTW_LAUNCH_GT4(NT_, CAP_, STG, BLOCKS, DYN)                                                                                             \
-                do {                                                                                                                            \
-                    if (tune.has_analytic) { if (stats) RTW_LAUNCH_GT(true, true, NT_, CAP_, STG, BLOCKS, DYN); else RTW_LAUNCH_GT(false, true, NT_, CAP_, STG, BLOCKS, DYN); } \
-                    else { if (stats) RTW_LAUNCH_GT(true, false, NT_, CAP_, STG, BLOCKS, DYN); else RTW_LAUNCH_GT(false, false, NT_, CAP_, STG, BLOCKS, DYN); } \
-                } while (0)
-                if (!tune.carry && trace_hint >= 0 && trace_hint < tune.wave_below) {
-                    // a short list: a wave per ray (128-thread blocks, a wave takes rays in turn)
-                    constexpr int NTV = 128;
-                    long long blocks = ((long long)trace_hint + trace_hint / 4 + 64 + NTV / 64 - 1) / (NTV / 64);
-                    const long long cap = (long long)tune.cu_count * 64;
-                    if (blocks < 1) blocks = 1;
-                    if (blocks > cap) blocks = cap;
-                    const size_t dyn = (size_t)(NTV / 64) * RTW_WAVE_LDS_WORDS * 4;
-                    if (tune.has_analytic) {
-                        if (stats) hipLaunchKernelGGL((gtrace_wave_kernel<true, true, NTV>), dim3((unsigned)blocks), dim3(NTV), dyn, stream, sc, gb, r - 1, 0, p.lead_shapes);
-                        else hipLaunchKernelGGL((gtrace_wave_kernel<false, true, NTV>), dim3((unsigned)blocks), dim3(NTV), dyn, stream, sc, gb, r - 1, 0, p.lead_shapes);
-                    } else {
-                        if (stats) hipLaunchKernelGGL((gtrace_wave_kernel<true, false, NTV>), dim3((unsigned)blocks), dim3(NTV), dyn, stream, sc, gb, r - 1, 0, p.lead_shapes);
-                        else hipLaunchKernelGGL((gtrace_wave_kernel<false, false, NTV>), dim3((unsigned)blocks), dim3(NTV), dyn, stream, sc, gb, r - 1, 0, p.lead_shapes);
-                    }
-                } else if ((tune.single_mesh || tune.lead_mesh) && tune.staged_top > 0) {
-                    // one mesh: persistent waves that refill their lanes (one block per CU when the tree's upper levels are staged)
-                    const int budget_r = tune.visit_budget;
-#define RTW_LAUNCH_GPL(NT_, CAP_, STG, LD, PL, BLOCKS, DYN)                                                                                      \
-                    do {                                                                                                                        \
-                        if (stats) { if ((DYN) > 65536) (void)hipFuncSetAttribute((const void*)gtrace_persist_kernel<true, NT_, CAP_, STG, LD, PL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(DYN)); \
-                            hipLaunchKernelGGL((gtrace_persist_kernel<true, NT_, CAP_, STG, LD, PL>), dim3(BLOCKS), dim3(NT_), (DYN), stream, sc, gb, r - 1, budget_r, tune.staged_shape); } \
-                        else { if ((DYN) > 65536) (void)hipFuncSetAttribute((const void*)gtrace_persist_kernel<false, NT_, CAP_, STG, LD, PL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(DYN)); \
-                            hipLaunchKernelGGL((gtrace_persist_kernel<false, NT_, CAP_, STG, LD, PL>), dim3(BLOCKS), dim3(NT_), (DYN), stream, sc, gb, r - 1, budget_r, tune.staged_shape); } \
-                    } while (0)
-#define RTW_LAUNCH_GP(NT_, CAP_, STG, PL, BLOCKS, DYN) do { if (tune.lead_mesh) RTW_LAUNCH_GPL(NT_, CAP_, STG, true, PL, BLOCKS, DYN); else RTW_LAUNCH_GPL(NT_, CAP_, STG, false, PL, BLOCKS, DYN); } while (0)
-                    {
-                        unsigned sbl = (tb + 3) / 4;
-                        if (sbl > (unsigned)tune.cu_count) sbl = (unsigned)tune.cu_count;
-                        const size_t dyn = (size_t)RTW_GT_CAP_STAGED * 1024 * 4 + (size_t)tune.staged_top * 32;
-                        if (tune.staged_all && tune.staged_planes) RTW_LAUNCH_GP(1024, RTW_GT_CAP_STAGED, 2, true, sbl, dyn + (size_t)tune.staged_tris * 16);
-                        else if (tune.staged_all) RTW_LAUNCH_GP(1024, RTW_GT_CAP_STAGED, 2, false, sbl, dyn);
-                        else RTW_LAUNCH_GP(1024, RTW_GT_CAP_STAGED, 1, false, sbl, dyn);
-                    }
-#undef RTW_LAUNCH_GP
-#undef RTW_LAUNCH_GPL
-                    if (tune.visit_budget < INT32_MAX) {        // the rays that ran out of budget: a wave each
-                        constexpr int NTV = 128;
-                        // a generous grid: the count varies from group to group, a wave-per-ray loop with too few waves is slow (measured: 0.9 ms for a few
-                        // thousand rays on 256 waves), blocks without a ray leave at once
-                        long long want = tune.overflow_hint[r - 1] >= 0 ? (long long)tune.overflow_hint[r - 1] * 4 + 8192 : 16384;
-                        long long blocks = (want + NTV / 64 - 1) / (NTV / 64);
-                        const long long cap = (long long)tune.cu_count * 64;
-                        if (blocks > cap) blocks = cap;
-                        const size_t dyn = (size_t)(NTV / 64) * RTW_WAVE_LDS_WORDS * 4;
-                        if (tune.lead_mesh) {
-                            if (stats) hipLaunchKernelGGL((gtrace_wave_kernel<true, true, NTV>), dim3((unsigned)blocks), dim3(NTV), dyn, stream, sc, gb, r - 1, 1, p.lead_shapes);
-                            else hipLaunchKernelGGL((gtrace_wave_kernel<false, true, NTV>), dim3((unsigned)blocks), dim3(NTV), dyn, stream, sc, gb, r - 1, 1, p.lead_shapes);
-                        } else {
-                            if (stats) hipLaunchKernelGGL((gtrace_wave_kernel<true, false, NTV>), dim3((unsigned)blocks), dim3(NTV), dyn, stream, sc, gb, r - 1, 1, 0);
-                            else hipLaunchKernelGGL((gtrace_wave_kernel<false, false, NTV>), dim3((unsigned)blocks), dim3(NTV), dyn, stream, sc, gb, r - 1, 1, 0);
-                        }
-                    }
-                } else if (tune.staged_shape >= 0 && tune.staged_top > 0) {
-                    const unsigned sbl = (tb + 3) / 4;          // 1024-thread blocks
-                    const size_t dyn = (size_t)RTW_GT_CAP_STAGED * 1024 * 4 + (size_t)tune.staged_top * 32;
-                    if (tune.staged_all) RTW_LAUNCH_GT4(1024, RTW_GT_CAP_STAGED, 2, sbl, dyn);
-                    else RTW_LAUNCH_GT4(1024, RTW_GT_CAP_STAGED, 1, sbl, dyn);
-                } else {
-                    const size_t dyn = (size_t)RTW_GT_CAP * 256 * 4;
-                    RTW_LAUNCH_GT4(256, RTW_GT_CAP, 0, tb, dyn);
-                }
-#undef RTW_LAUNCH_GT4
-#undef RTW_LAUNCH_GT
-                }
-                if (tune.has_analytic) {
-                    if (stats) hipLaunchKernelGGL((gshade_kernel<true, true>), dim3(sb_full), dim3(256), 0, stream, sc, gb, g, r);
-                    else hipLaunchKernelGGL((gshade_kernel<false, true>), dim3(sb_full), dim3(256), 0, stream, sc, gb, g, r);
-                } else {
-                    if (stats) hipLaunchKernelGGL((gshade_kernel<true, false>), dim3(sb_full), dim3(256), 0, stream, sc, gb, g, r);
-                    else hipLaunchKernelGGL((gshade_kernel<false, false>), dim3(sb_full), dim3(256), 0, stream, sc, gb, g, r);
-                }
-            }
+            with_flags(stats, tune.has_analytic, [&](auto ST, auto AN) {
+                launch(gshade_kernel<decltype(ST)::value, decltype(AN)::value>, dim3(sb_full), dim3(256), 0, stream, sc, gb, g, r);
+            });
         }
         if (tune.timing) (void)hipEventRecord(tune.timing[2], stream);
         if (tune.resolve_after) (void)hipStreamWaitEvent(stream, tune.resolve_after, 0);      // a pixel's passes are added in pass order
-        hipLaunchKernelGGL(gresolve_kernel, dim3((unsigned)((g.n_busy + 3) / 4)), dim3(256), 0, stream, sc, (float4*)accum, (uint32_t*)argb, gb, g);
+        launch(gresolve_kernel, dim3((unsigned)((g.n_busy + 3) / 4)), dim3(256), 0, stream, sc, (float4*)accum, (uint32_t*)argb, gb, g);
         if (tune.resolve_done) (void)hipEventRecord(tune.resolve_done, stream);
     } else if (tune.timing) {
         (void)hipEventRecord(tune.timing[1], stream); (void)hipEventRecord(tune.timing[2], stream);
     }
-    if (forked && tune.do_join) {
-        (void)hipStreamWaitEvent(stream, tune.join_event, 0);
-        if (tune.aux_unjoined) *tune.aux_unjoined = false;
-    }
+    join_sky(tune, forked, stream);
     if (tune.timing) (void)hipEventRecord(tune.timing[3], stream);
     return (int)hipGetLastError();
 }
@@ -1774,8 +1708,7 @@ int launch_closest(const RtwSceneDev* sc, const float* rays, long long n, float*
     if (n <= 0) return 0;
     const int block = 256;
     const unsigned grid = (unsigned)((n + block - 1) / block);
-    if (stats) hipLaunchKernelGGL(closest_kernel<true>, dim3(grid), dim3(block), 0, stream, sc, rays, n, hits11, shape, tri);
-    else hipLaunchKernelGGL(closest_kernel<false>, dim3(grid), dim3(block), 0, stream, sc, rays, n, hits11, shape, tri);
+    with_flags(stats, [&](auto ST) { launch(closest_kernel<decltype(ST)::value>, dim3(grid), dim3(block), 0, stream, sc, rays, n, hits11, shape, tri); });
     return (int)hipGetLastError();
 }
 
@@ -1805,32 +1738,15 @@ int launch_query(const RtwSceneDev* sc, const float* rays, long long n, float* h
 {
     if (n <= 0) return 0;
     int nt; unsigned blocks;
-    const bool any = occluded != nullptr, an = !q.single_mesh;
     query_launch_shape(q, n, &nt, &blocks);
     const int carry = q.carry ? 1 : 0;
-#define RTW_LAUNCH_Q(ST, AN_, NT_, CAP_, STG, ANY_, DYN)                                                                                          \
-    do {                                                                                                                                        \
-        static bool lds_raised = false;      /* once per instantiation, to the most any scene can ask for (candidate lists + RTW_TNODES_TOP_BUDGET records) */ \
-        if (STG != 0 && !lds_raised) { (void)hipFuncSetAttribute((const void*)qtrace_kernel<ST, AN_, NT_, CAP_, STG, ANY_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)(CAP_) * (NT_) * 4 + (size_t)RTW_TNODES_TOP_BUDGET * 32)); lds_raised = true; } \
-        hipLaunchKernelGGL((qtrace_kernel<ST, AN_, NT_, CAP_, STG, ANY_>), dim3(blocks), dim3(NT_), (DYN), stream, sc, rays, (uint32_t)n, hits11, shape, tri, occluded, q.staged_shape, carry); \
-    } while (0)
-#define RTW_LAUNCH_Q2(ST, AN_, NT_, CAP_, STG, DYN) do { if (any) RTW_LAUNCH_Q(ST, AN_, NT_, CAP_, STG, true, DYN); else RTW_LAUNCH_Q(ST, AN_, NT_, CAP_, STG, false, DYN); } while (0)
-#define RTW_LAUNCH_Q4(NT_, CAP_, STG, DYN)                                                                                                       \
-    do {                                                                                                                                        \
-        if (an) { if (stats) RTW_LAUNCH_Q2(true, true, NT_, CAP_, STG, DYN); else RTW_LAUNCH_Q2(false, true, NT_, CAP_, STG, DYN); }             \
-        else { if (stats) RTW_LAUNCH_Q2(true, false, NT_, CAP_, STG, DYN); else RTW_LAUNCH_Q2(false, false, NT_, CAP_, STG, DYN); }              \
-    } while (0)
-    if (nt == 1024) {
-        const size_t dyn = (size_t)RTW_GT_CAP_STAGED * 1024 * 4 + (size_t)q.staged_top * 32;
-        if (q.staged_all) RTW_LAUNCH_Q4(1024, RTW_GT_CAP_STAGED, 2, dyn);
-        else RTW_LAUNCH_Q4(1024, RTW_GT_CAP_STAGED, 1, dyn);
-    } else {
-        const size_t dyn = (size_t)RTW_GT_CAP * 256 * 4;
-        RTW_LAUNCH_Q4(256, RTW_GT_CAP, 0, dyn);
-    }
-#undef RTW_LAUNCH_Q4
-#undef RTW_LAUNCH_Q2
-#undef RTW_LAUNCH_Q
+    with_trace_shape(nt == 1024, q.staged_all, [&](auto SH) {
+        using S = decltype(SH);
+        with_flags(stats, !q.single_mesh, occluded != nullptr, [&](auto ST, auto AN, auto ANY) {
+            launch(qtrace_kernel<decltype(ST)::value, decltype(AN)::value, S::NT, S::CAP, S::STG, decltype(ANY)::value>, dim3(blocks), dim3(S::NT), S::lds(q.staged_top), stream,
+                   sc, rays, (uint32_t)n, hits11, shape, tri, occluded, q.staged_shape, carry);
+        });
+    });
     return (int)hipGetLastError();
 }
 
@@ -1840,8 +1756,7 @@ int launch_ray_trace(const RtwSceneDev* sc, const float* rays, const uint32_t* k
     if (n <= 0) return 0;
     const int block = 256;
     const unsigned grid = (unsigned)((n + block - 1) / block);
-    if (stats) hipLaunchKernelGGL(ray_trace_kernel<true>, dim3(grid), dim3(block), 0, stream, sc, rays, keys2, n, max_bounce, preview, seed, npix, rgb, (float4*)ws);
-    else hipLaunchKernelGGL(ray_trace_kernel<false>, dim3(grid), dim3(block), 0, stream, sc, rays, keys2, n, max_bounce, preview, seed, npix, rgb, (float4*)ws);
+    with_flags(stats, [&](auto ST) { launch(ray_trace_kernel<decltype(ST)::value>, dim3(grid), dim3(block), 0, stream, sc, rays, keys2, n, max_bounce, preview, seed, npix, rgb, (float4*)ws); });
     return (int)hipGetLastError();
 }
 
@@ -1875,8 +1790,7 @@ int launch_gather_rows(bool unpack, void* argb, void* accum, void* stage, int wi
     if (gx < 1u) gx = 1u;
     if (gx > 4096u) gx = 4096u;
     const dim3 grid(gx, (unsigned)b.n);
-    if (unpack) { if (vec) hipLaunchKernelGGL((gather_rows_kernel<true, true>), grid, dim3(256), 0, stream, g); else hipLaunchKernelGGL((gather_rows_kernel<true, false>), grid, dim3(256), 0, stream, g); }
-    else { if (vec) hipLaunchKernelGGL((gather_rows_kernel<false, true>), grid, dim3(256), 0, stream, g); else hipLaunchKernelGGL((gather_rows_kernel<false, false>), grid, dim3(256), 0, stream, g); }
+    with_flags(unpack, vec, [&](auto UNPACK, auto VEC) { launch(gather_rows_kernel<decltype(UNPACK)::value, decltype(VEC)::value>, grid, dim3(256), 0, stream, g); });
     return (int)hipGetLastError();
 }
 

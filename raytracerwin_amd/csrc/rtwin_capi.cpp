@@ -89,8 +89,7 @@ struct rtw_context {
     bool own_stream = false;
     hipStream_t aux_stream = nullptr;   // sky-only tiles of the bins + wave pipeline run here, beside the main stream
     hipEvent_t fork_event = nullptr, join_event = nullptr;
-    int batch_pos = 0;                  // rtw_render_passes: 0 = a pass on its own, 1 = first of a run, 2 = inside a run, 3 = last of a run
-    bool aux_unjoined = false;          // a sky kernel of the current run is not joined yet
+    bool aux_unjoined = false;          // a sky kernel of the current run of passes (rtw_render_passes) is not joined yet
     float* d_unit = nullptr;
     float* d_gamma = nullptr;
     float* d_lut = nullptr;
@@ -125,9 +124,7 @@ struct rtw_context {
     int group_parts = 2;                      // option: parts a split group runs as, at most (measured on C2 / C4 at 20 passes: 2 parts -8 % / -1 % against one, 3 and 4 parts +10..25 %)
     int group_split = 1, split_min = 8;       // options: halves when a group has at least split_min passes ...
     int split_paths = 400000;                 // ... and each half at least this many paths (a rank's share of a small frame at 8 ranks stays whole: measured 0.0123 whole, 0.0144 ms split)
-    bool lane_sky_only = false;
     int sky_blocks = 4;                 // the sky kernel's blocks per CU at most (its lanes loop over the tiles); 1, 2, 4, 16 measured: all within 1.5 % on C2 / C4, at 1 and 20 passes per call
-    int lane = 0, lane_count = 1, lane_sky_passes = 0, lane_sky_first = 0;        // set by rtw_render_passes around render_group: which part of how many; the whole group's passes (the parts share out its sky tiles)
     uint32_t* h_gcounters = nullptr;    // pinned: list lengths of a finished group
     hipEvent_t gcounters_event = nullptr;
     bool gcounters_pending = false;
@@ -148,9 +145,6 @@ struct rtw_context {
     int device_build = 1;               // rtw_scene_commit builds the tree (KdNode::Build's decisions) and the layouts derived from it on the device (0: on the host)
     int last_pipeline = -1;             // the pipeline the latest render call actually ran (rtw_last_pass_pipeline)
     size_t workspace_limit = (size_t)24 << 30;  // a group's workspace may not exceed this (option "workspace_limit_mb"); hipMalloc failing counts as exceeding it
-    bool ws_refused = false;            // the latest ensure_group_workspace was refused (limit or out of memory): the caller retries with a smaller group
-    bool ws_single = false;             // the group at hand is one pass: the limit does not apply (only hipMalloc can refuse it)
-    int group_cap = 0;                  // > 0: groups of the current rtw_render_passes call hold at most this many passes (set after a refusal)
     int fallbacks = 0;                  // how many times a group was re-formed smaller after a refusal (rtw_context_memory_bytes' caller can see it: option-free diagnostics)
     // ray queries on device buffers (rtw_trace_closest_device / rtw_trace_occluded_device)
     int query_kernel = -1;              // option: 1 = qtrace_kernel, 0 = closest_kernel on the caller's buffers (the baseline and cross-check), -1 = the measured rule (query_uses_new_kernel)
@@ -168,6 +162,20 @@ struct rtw_scene {
     bool has_analytic = false;          // some shape is a sphere / plane / capsule
     bool texture_carry = false;         // ... and comes after a textured mesh: its hits can inherit that mesh's sampled colour
                                         // (one RayHitResult serves all shapes, Src/RayTracerScene.cpp:99-125) -> single-kernel pipeline
+    // What the launches of every pipeline and query need to know about the shape list, worked out once (rtw_scene_commit).  Whatever also depends on an
+    // option of the context (options can change between calls) is derived from these per call.
+    struct Facts {
+        int lead_shapes = 0;            // leading spheres / planes / capsules / triangles: the lane that sets a segment up tests them
+        bool all_lead = false;          // ... and they are the whole scene: nothing is left for a trace launch
+        bool single_mesh = false;       // the scene is one mesh (with a tree)
+        bool lead_then_mesh = false;    // the scene is leading shapes followed by exactly one mesh (with a tree)
+        int staged_shape = -1;          // the first mesh whose upper tree levels the trace blocks stage in LDS (-1: none) ...
+        int staged_top = 0;             // ... how many tnodes records of it ...
+        bool staged_all = false;        // ... whether that is its whole tree ...
+        int staged_tris = 0;            // ... and its triangles
+        size_t last_nodes = 0;          // tree nodes of the last shape (the mesh of the two one-mesh forms above)
+        bool big_tree = false;          // some tree has more than 4 096 nodes
+    } facts;
     int prune = 1;
     int traversal = 1;
     RtwCamera camera = rtw_default_camera();    // rtw_scene_set_camera; travels by value in every launch's parameters
@@ -818,6 +826,25 @@ int rtw_scene_commit(rtw_scene* scene)
     scene->allocs.push_back(dsc);
     HIP_TRY(hipMemcpy(dsc, h.get(), sizeof(RtwSceneDev), hipMemcpyHostToDevice));
     scene->d_scene = (RtwSceneDev*)dsc;
+    {
+        rtw_scene::Facts f;
+        const auto& ms = scene->meshes;
+        const int n = (int)ms.size();
+        auto is_mesh = [&](int k) { return ms[(size_t)k]->kind == RTW_SHAPE_MESH; };
+        while (f.lead_shapes < n && !is_mesh(f.lead_shapes)) f.lead_shapes++;
+        f.all_lead = n > 0 && f.lead_shapes == n;
+        const bool ends_in_tree = n > 0 && is_mesh(n - 1) && !ms.back()->nodes.empty();
+        f.single_mesh = n == 1 && ends_in_tree;
+        f.lead_then_mesh = f.lead_shapes > 0 && f.lead_shapes == n - 1 && ends_in_tree;
+        for (int k = 0; k < n && f.staged_shape < 0; k++)
+            if (is_mesh(k) && ms[(size_t)k]->tnodes_top > 0) {
+                f.staged_shape = k; f.staged_top = ms[(size_t)k]->tnodes_top;
+                f.staged_all = f.staged_top == (int)ms[(size_t)k]->tnodes.size(); f.staged_tris = (int)ms[(size_t)k]->tris.size();
+            }
+        f.last_nodes = n > 0 ? ms.back()->nodes.size() : 0;
+        for (const auto& m : ms) if (m->nodes.size() > 4096) f.big_tree = true;
+        scene->facts = f;
+    }
     scene->allocs_at_commit = scene->allocs.size();
     scene->committed = true;
     return RTW_OK;
@@ -958,13 +985,9 @@ QueryShape::QueryShape(const rtw_scene* scene)
     const rtw_context* cx = scene->ctx;
     rtw::QueryTuning& q = *this;
     q.cu_count = cx->cu_count; q.blocks = cx->query_blocks;
-    q.single_mesh = scene->meshes.size() == 1 && scene->meshes[0]->kind == RTW_SHAPE_MESH && !scene->meshes[0]->nodes.empty();
+    q.single_mesh = scene->facts.single_mesh;
     q.carry = scene->texture_carry;
-    for (size_t k = 0; k < scene->meshes.size(); k++)       // the first mesh's upper tree levels live in the blocks' LDS, as in the render path
-        if (scene->meshes[k]->kind == RTW_SHAPE_MESH && scene->meshes[k]->tnodes_top > 0) {
-            q.staged_shape = (int)k; q.staged_top = scene->meshes[k]->tnodes_top; q.staged_all = q.staged_top == (int)scene->meshes[k]->tnodes.size();
-            break;
-        }
+    q.staged_shape = scene->facts.staged_shape; q.staged_top = scene->facts.staged_top; q.staged_all = scene->facts.staged_all;
 }
 // Which kernel a device query runs.  "query_kernel" -1 (the default) is the rule the interleaved A/B of tools/query_bench.py gave (profiles/query_experiments.md:
 // the new kernel wherever its median beat the old kernel's by more than the old kernel's own spread, the old kernel elsewhere):
@@ -1392,28 +1415,31 @@ static int scene_group_table(rtw_scene* scene, rtw_scene::BinSet& bs, const RtwR
     return RTW_OK;
 }
 
-static int ensure_group_workspace(rtw_context* cx, size_t bytes)
+// The workspace of part `part` holds `bytes` (grow-only).  single: the group at hand is one pass, the limit does not apply (only hipMalloc can refuse it).
+// *refused (never null) tells a refusal -- the limit, or no room on the device: the caller forms a smaller group -- from any other failure.
+static int ensure_group_workspace(rtw_context* cx, int part, size_t bytes, bool single, bool* refused)
 {
-    void*& ws = cx->d_group_ws[cx->lane];
-    size_t& have = cx->group_ws_bytes[cx->lane];
-    cx->ws_refused = false;
+    void*& ws = cx->d_group_ws[part];
+    size_t& have = cx->group_ws_bytes[part];
+    *refused = false;
     if (bytes <= have) return RTW_OK;
-    if (bytes > cx->workspace_limit && !cx->ws_single) { cx->ws_refused = true; return fail(RTW_ERR_HIP, "group workspace above the context's workspace limit"); }      // (a one-pass group is always tried: the limit shapes groups, it does not refuse frames)
-    // grow-only; growing waits for the streams (rtw_render_reserve does it ahead of a call that must not stall)
+    if (bytes > cx->workspace_limit && !single) { *refused = true; return fail(RTW_ERR_HIP, "group workspace above the context's workspace limit"); }      // (a one-pass group is always tried: the limit shapes groups, it does not refuse frames)
+    // growing waits for the streams (rtw_render_reserve does it ahead of a call that must not stall)
     HIP_TRY(hipStreamSynchronize(cx->stream));
     if (cx->aux_stream) HIP_TRY(hipStreamSynchronize(cx->aux_stream));
     for (int j = 1; j < RTW_MAX_PARTS; j++) if (cx->part_stream[j]) HIP_TRY(hipStreamSynchronize(cx->part_stream[j]));
     if (ws) { (void)hipFree(ws); ws = nullptr; have = 0; }
-    cx->group_clean[cx->lane] = false;
+    cx->group_clean[part] = false;
     const hipError_t e = hipMalloc(&ws, bytes);
-    if (e != hipSuccess) {      // no room on the device (a GPU shared with torch, other ranks ...): the caller forms a smaller group
+    if (e != hipSuccess) {      // no room on the device (a GPU shared with torch, other ranks ...)
         ws = nullptr; (void)hipGetLastError();
-        cx->ws_refused = true;
+        *refused = true;
         return hip_fail(e, "hipMalloc of the group workspace");
     }
     have = bytes;
     return RTW_OK;
 }
+
 
 static int check_render_args(const rtw_scene* scene, const rtw_framebuffer* fb, int max_bounce, int pass_index, int sub_samples)
 {
@@ -1445,21 +1471,45 @@ static int group_passes(const rtw_context* cx, long long paths_per_pass, int rem
     return (int)(k < remaining ? k : remaining);
 }
 
-// The next group of a call: how many of the `remaining` passes it takes (the policy above, under the cap a refusal of workspace has set) and whether it
-// runs as two halves on two streams.
-static int next_group(const rtw_context* cx, long long per_pass, int remaining, int max_bounce, bool carry, bool preview, int* parts)
-{
-    *parts = 1;
-    if (preview) return 1;
-    int k = group_passes(cx, per_pass > 0 ? per_pass : 1, remaining, max_bounce, carry);
-    if (cx->group_cap > 0 && k > cx->group_cap) k = cx->group_cap;
-    if (cx->group_split && k >= cx->split_min && !cx->stats_enabled && !cx->kernel_timing) {
-        // as many parts as the option allows, each with at least split_min / 2 passes and split_paths paths
-        int n = cx->group_parts;
-        while (n > 1 && (k / n < (cx->split_min + 1) / 2 || per_pass * (k / n) < cx->split_paths)) n--;
-        *parts = n;
+// The groups a call of n_passes passes forms, in order: rtw_render_passes renders them, rtw_render_reserve sizes the workspaces for them.
+//   for (GroupWalk w{...}; w.next(); w.done += w.k) ...      (a refused group: set w.cap and ask again without advancing)
+struct GroupWalk {
+    const rtw_context* cx; long long per_pass; int n_passes, max_bounce; bool carry, preview;
+    int done = 0;
+    int cap = 0;                // > 0: the groups still to come hold at most this many passes (the owner of the loop sets it after a refusal of workspace)
+    int k = 0, parts = 1;       // the group at hand: its passes (the policy of group_passes, under the cap) and how many parts on as many streams it runs as
+    bool next()
+    {
+        if (done >= n_passes) return false;
+        k = 1; parts = 1;
+        if (preview) return true;
+        k = group_passes(cx, per_pass > 0 ? per_pass : 1, n_passes - done, max_bounce, carry);
+        if (cap > 0 && k > cap) k = cap;
+        if (cx->group_split && k >= cx->split_min && !cx->stats_enabled && !cx->kernel_timing) {
+            // as many parts as the option allows, each with at least split_min / 2 passes and split_paths paths
+            parts = cx->group_parts;
+            while (parts > 1 && (k / parts < (cx->split_min + 1) / 2 || per_pass * (k / parts) < cx->split_paths)) parts--;
+        }
+        return true;
     }
-    return k;
+    bool first() const { return done == 0; }
+    bool last() const { return done + k >= n_passes; }
+    int part_passes(int j) const { return k / parts + (j < k % parts ? 1 : 0); }
+    size_t part_bytes() const { return rtw::group_workspace_bytes(rtw::group_capacity((size_t)per_pass, part_passes(0)), max_bounce, carry, nullptr); }     // of the largest part
+};
+
+// The rank's share of the frame: every world-th task of task_rows rows, from task `rank` on (begin, count, task_rows, rank, world of *p; the rest zeroed).
+static int rank_share(const rtw_framebuffer* fb, int task_rows, int rank, int world, RtwRenderParams* p)
+{
+    if (task_rows < 1 || world < 1 || rank < 0 || rank >= world) return fail(RTW_ERR_INVALID, "bad task partition");
+    std::memset(p, 0, sizeof *p);
+    const int n_tasks = (fb->height + task_rows - 1) / task_rows;
+    const int mine = n_tasks > rank ? (n_tasks - rank + world - 1) / world : 0;
+    p->begin = 0; p->task_rows = task_rows; p->rank = rank; p->world = world;
+    const int64_t cnt = world == 1 ? (int64_t)fb->width * fb->height : (int64_t)mine * task_rows * fb->width;
+    if (cnt > INT32_MAX) return fail(RTW_ERR_LIMIT, "too many work items");
+    p->count = (int)cnt;
+    return RTW_OK;
 }
 
 // what rtw_render_passes and rtw_render_reserve share: the rank's share of the frame and its paths per pass (busy tiles x 64 x sub-samples; builds the
@@ -1468,16 +1518,9 @@ struct GroupCall { RtwRenderParams p; long long per_pass; };
 static int plan_group_call(rtw_scene* scene, rtw_framebuffer* fb, int task_rows, int rank, int world, int max_bounce, int first_pass, int sub_samples, GroupCall* out)
 {
     rtw_context* cx = scene->ctx;
-    if (task_rows < 1 || world < 1 || rank < 0 || rank >= world) return fail(RTW_ERR_INVALID, "bad task partition");
-    int rc = check_render_args(scene, fb, max_bounce, first_pass, sub_samples); if (rc != RTW_OK) return rc;
-    RtwRenderParams p; std::memset(&p, 0, sizeof p);
-    const int n_tasks = (fb->height + task_rows - 1) / task_rows;
-    const int mine = n_tasks > rank ? (n_tasks - rank + world - 1) / world : 0;
-    p.begin = 0; p.task_rows = task_rows; p.rank = rank; p.world = world;
-    const int64_t cnt = world == 1 ? (int64_t)fb->width * fb->height : (int64_t)mine * task_rows * fb->width;
-    if (cnt > INT32_MAX) return fail(RTW_ERR_LIMIT, "too many work items");
-    p.count = (int)cnt;
-    out->p = p;
+    int rc = rank_share(fb, task_rows, rank, world, &out->p); if (rc != RTW_OK) return rc;
+    rc = check_render_args(scene, fb, max_bounce, first_pass, sub_samples); if (rc != RTW_OK) return rc;
+    const RtwRenderParams& p = out->p;
     // paths per pass: the busy tiles' pixels x sub-samples (known once the tile lists exist; the whole share until then)
     long long per_pass = (long long)p.count * sub_samples;
     if (p.count > 0) {
@@ -1490,14 +1533,49 @@ static int plan_group_call(rtw_scene* scene, rtw_framebuffer* fb, int task_rows,
     return RTW_OK;
 }
 
-// One group: passes first_pass .. first_pass + n_passes - 1 over the pixels begin .. end of this rank's share of the frame.
-// ranged: a pixel range (rtw_render_range), else the whole frame / the rank's tasks.  batch_pos as rtw_context::batch_pos.
-static int render_group(rtw_scene* scene, rtw_framebuffer* fb, RtwRenderParams p, bool ranged, int range_begin, int range_end,
-                        int max_bounce, int use_base_color, int first_pass, int n_passes, int sub_samples, uint32_t seed)
+// Where a pass or group stands in the run of passes one rtw_render_passes call makes: the run forks the second stream before its first and joins it after its last.
+enum RunPos { RUN_ALONE, RUN_FIRST, RUN_INSIDE, RUN_LAST };
+static RunPos run_pos(bool first, bool last) { return first ? (last ? RUN_ALONE : RUN_FIRST) : (last ? RUN_LAST : RUN_INSIDE); }
+static void set_aux_fork(rtw_context* cx, RunPos pos, rtw::AuxFork* t)
+{
+    t->aux_stream = cx->aux_stream; t->fork_event = cx->fork_event; t->join_event = cx->join_event;
+    t->do_fork = pos == RUN_ALONE || pos == RUN_FIRST || !cx->aux_unjoined;      // (a run whose earlier passes launched no sky kernel has not forked yet)
+    t->do_join = pos == RUN_ALONE || pos == RUN_LAST; t->aux_unjoined = &cx->aux_unjoined;
+}
+// a run ends (an error, or a last pass or group that launched no sky kernel) with a sky kernel not joined yet
+static void end_run(rtw_context* cx)
+{
+    if (!cx->aux_unjoined) return;
+    (void)hipEventRecord(cx->join_event, cx->aux_stream);
+    (void)hipStreamWaitEvent(cx->stream, cx->join_event, 0);
+    cx->aux_unjoined = false;
+}
+
+// One launch of the pass-batched pipeline.
+struct GroupRequest {
+    RtwRenderParams share;              // the share of the frame: begin, count and the task partition
+    bool ranged = false;                // a pixel range (rtw_render_range), else the whole frame / the rank's tasks
+    int range_begin = 0, range_end = 0;
+    int first_pass = 0, n_passes = 1;   // passes first_pass .. first_pass + n_passes - 1
+    int max_bounce = 0, use_base_color = 0, sub_samples = 1; uint32_t seed = 0;
+    // a group split into parts on as many streams (rtw_render_passes): this is part `part` of `parts`, with workspace and stream `part`; the group's sky
+    // tiles get all its passes (sky_first, sky_passes) from ONE launch enqueued ahead of the parts (sky_only), which touches no workspace
+    int part = 0, parts = 1, sky_first = 0, sky_passes = 0; bool sky_only = false;
+    RunPos pos = RUN_ALONE;
+};
+
+
+// One launch of the pass-batched pipeline: the passes of `q` over its share of the frame.  *refused as ensure_group_workspace.
+static int render_group(rtw_scene* scene, rtw_framebuffer* fb, const GroupRequest& q, bool* refused)
 {
     rtw_context* cx = scene->ctx;
+    const rtw_scene::Facts& facts = scene->facts;
+    *refused = false;
+    RtwRenderParams p = q.share;
+    const int range_begin = q.range_begin, range_end = q.range_end, max_bounce = q.max_bounce, first_pass = q.first_pass, n_passes = q.n_passes, sub_samples = q.sub_samples;
+    bool ranged = q.ranged;
     p.width = fb->width; p.height = fb->height;
-    p.max_bounce = max_bounce; p.preview = use_base_color ? 1 : 0; p.pass_index = first_pass; p.sub_samples = sub_samples; p.seed = seed;
+    p.max_bounce = max_bounce; p.preview = q.use_base_color ? 1 : 0; p.pass_index = first_pass; p.sub_samples = sub_samples; p.seed = q.seed;
     p.cam = scene->camera; p.cam_general = camera_is_default(scene->camera) ? 0 : 1;
     if (!choose_group_tiles(p, range_begin, range_end)) return fail(RTW_ERR_LIMIT, "frame too large for the tile mapping");
     rtw_scene::BinSet* bs = nullptr;
@@ -1516,11 +1594,7 @@ static int render_group(rtw_scene* scene, rtw_framebuffer* fb, RtwRenderParams p
         g.n_busy = gt->n_busy; g.n_sky = gt->n_sky; g.n_jobs = gt->n_jobs;
         g.busy_tiles = gt->d_busy; g.sky_tiles = gt->d_sky; g.jobs = gt->d_jobs;
     }
-    {   // the scene's leading spheres / planes / capsules / triangles are tested by the lane that sets a segment up (group_lead_query)
-        int lead = 0;
-        while (lead < (int)scene->meshes.size() && scene->meshes[(size_t)lead]->kind != RTW_SHAPE_MESH) lead++;
-        p.lead_shapes = lead;
-    }
+    p.lead_shapes = facts.lead_shapes;      // tested by the lane that sets a segment up (group_lead_query)
     g.rp = p;
     // the primary kernel's waves: the bin of a tile is walked once for up to four rays per lane (its sub-samples and / or several passes) -- as many
     // passes per wave as still leave the launch about two rounds of waves (C2 at 20 passes: 2 per wave 0.0367, 4 per wave 0.0376 ms per pass; at 192: 4 wins)
@@ -1535,48 +1609,36 @@ static int render_group(rtw_scene* scene, rtw_framebuffer* fb, RtwRenderParams p
     const bool carry = scene->texture_carry;
     const size_t capacity = rtw::group_capacity((size_t)g.n_busy * 64 * (size_t)sub_samples, n_passes);
     if (capacity >= ((size_t)1 << 31)) return fail(RTW_ERR_LIMIT, "too many paths in one launch");
-    // the workspace of THIS group (grow-only): a caller that must not stall inside a later, longer call reserves it with rtw_render_reserve
-    cx->ws_single = n_passes == 1 && cx->lane_count == 1;
-    rc = ensure_group_workspace(cx, rtw::group_workspace_bytes(capacity, max_bounce, carry, nullptr));
-    cx->ws_single = false;
+    // the workspace of THIS launch (grow-only): a caller that must not stall inside a later, longer call reserves it with rtw_render_reserve
+    rc = ensure_group_workspace(cx, q.part, rtw::group_workspace_bytes(capacity, max_bounce, carry, nullptr), n_passes == 1 && q.parts == 1, refused);
     if (rc != RTW_OK) return rc;
     rtw::GroupTuning tune;
     tune.capacity = capacity;
-    tune.aux_stream = cx->aux_stream; tune.fork_event = cx->fork_event; tune.join_event = cx->join_event;
-    tune.do_fork = cx->batch_pos == 0 || cx->batch_pos == 1 || !cx->aux_unjoined;
-    tune.do_join = cx->batch_pos == 0 || cx->batch_pos == 3; tune.aux_unjoined = &cx->aux_unjoined;
+    set_aux_fork(cx, q.pos, &tune);
     tune.gamma_thr = cx->d_gamma;
     tune.has_analytic = scene->has_analytic; tune.carry = carry;
-    tune.counters_clean = cx->group_clean[cx->lane];
-    if (cx->lane_count > 1) {       // a part of a split group: no sky tiles (the group's sky kernel was enqueued ahead of the parts, see rtw_render_passes); its resolve kernel after the previous part's
-        tune.sky_passes = cx->lane_sky_passes; tune.sky_first_pass = cx->lane_sky_first;
-        tune.sky_mode = cx->lane_sky_only ? 2 : 1;
+    tune.counters_clean = cx->group_clean[q.part];
+    if (q.parts > 1) {       // a part of a split group: no sky tiles (the group's sky kernel was enqueued ahead of the parts, see rtw_render_passes); its resolve kernel after the previous part's
+        tune.sky_passes = q.sky_passes; tune.sky_first_pass = q.sky_first;
+        tune.sky_mode = q.sky_only ? 2 : 1;
         tune.aux_stream = nullptr;
-        tune.resolve_after = cx->lane > 0 ? cx->part_resolved[cx->lane - 1] : nullptr;
-        tune.resolve_done = cx->part_resolved[cx->lane];
+        tune.resolve_after = q.part > 0 ? cx->part_resolved[q.part - 1] : nullptr;
+        tune.resolve_done = cx->part_resolved[q.part];
     }
     tune.cu_count = cx->cu_count; tune.sky_blocks = cx->sky_blocks;
-    {      // the first mesh's upper tree levels live in the trace blocks' LDS
-        for (size_t k = 0; k < scene->meshes.size(); k++)
-            if (scene->meshes[k]->kind == RTW_SHAPE_MESH && scene->meshes[k]->tnodes_top > 0) { tune.staged_shape = (int)k; tune.staged_top = scene->meshes[k]->tnodes_top; tune.staged_all = tune.staged_top == (int)scene->meshes[k]->tnodes.size(); break; }
-    }
+    // the first mesh's upper tree levels live in the trace blocks' LDS
+    tune.staged_shape = facts.staged_shape; tune.staged_top = facts.staged_top; tune.staged_all = facts.staged_all;
     if (tune.staged_shape >= 0 && tune.staged_all) {        // ... and the triangles' planes beside a tree that lives in LDS entirely, if they fit (1 024-thread block: 32 KiB of candidate lists)
-        const size_t need = (size_t)RTW_PERSIST_CAND_BYTES + (size_t)tune.staged_top * 32 + scene->meshes[(size_t)tune.staged_shape]->tris.size() * 16;
+        const size_t need = (size_t)RTW_PERSIST_CAND_BYTES + (size_t)tune.staged_top * 32 + (size_t)facts.staged_tris * 16;
         tune.staged_planes = cx->backface_filter != 0 && need <= (size_t)150 * 1024;
-        tune.staged_tris = (int)scene->meshes[(size_t)tune.staged_shape]->tris.size();
+        tune.staged_tris = facts.staged_tris;
     }
-    tune.single_mesh = scene->meshes.size() == 1 && scene->meshes[0]->kind == RTW_SHAPE_MESH && !scene->meshes[0]->nodes.empty();
-    tune.lead_mesh = !carry && p.lead_shapes > 0 && p.lead_shapes == (int)scene->meshes.size() - 1 && scene->meshes.back()->kind == RTW_SHAPE_MESH && !scene->meshes.back()->nodes.empty() &&
-                     tune.staged_shape == p.lead_shapes;
-
+    tune.single_mesh = facts.single_mesh;
+    tune.lead_mesh = !carry && facts.lead_then_mesh && tune.staged_shape == p.lead_shapes;
     // big trees: rays with very long walks (a few per cent need 4 x the mean) go to the wave-per-ray kernel instead of keeping a launch waiting
-    tune.visit_budget = (cx->visit_budget > 0 && (tune.single_mesh || tune.lead_mesh) && scene->meshes.back()->nodes.size() > (size_t)cx->budget_nodes) ? cx->visit_budget : INT32_MAX;
-    {   // long walks (a tree of more than 4 096 nodes): the wave-per-ray kernel pays up to longer lists
-        bool big = false;
-        for (const auto& m : scene->meshes) if (m->nodes.size() > 4096) big = true;
-        tune.wave_below = big ? cx->wave_below * 5 : cx->wave_below;
-    }
-    tune.timing = (cx->kernel_timing && cx->lane == 0) ? cx->timing_events : nullptr;
+    tune.visit_budget = (cx->visit_budget > 0 && (tune.single_mesh || tune.lead_mesh) && facts.last_nodes > (size_t)cx->budget_nodes) ? cx->visit_budget : INT32_MAX;
+    tune.wave_below = facts.big_tree ? cx->wave_below * 5 : cx->wave_below;       // long walks: the wave-per-ray kernel pays up to longer lists
+    tune.timing = (cx->kernel_timing && q.part == 0) ? cx->timing_events : nullptr;
     // list lengths of the latest finished group with the same shape (a stale or missing value only costs speed)
     // (keyed by the launch shape WITHOUT the number of passes: the lengths are kept per pass and scaled to the group at hand, so a warm-up call of any
     // length primes a longer one)
@@ -1593,18 +1655,18 @@ static int render_group(rtw_scene* scene, rtw_framebuffer* fb, RtwRenderParams p
     for (int r = 0; r < 32; r++) { tune.overflow_hint[r] = -1; tune.trace_hint[r] = -1; }
     for (int r = 0; r < 16; r++) tune.overflow_hint[r] = (cx->known_gkey == key) ? scaled(cx->known_goverflow[r]) : -1;
     for (int r = 0; r < 16; r++) tune.trace_hint[r] = (cx->known_gkey == key) ? scaled(cx->known_gtrace[r]) : -1;
-    tune.skip_trace = p.lead_shapes > 0 && p.lead_shapes == (int)scene->meshes.size();
-    bool& clean = cx->group_clean[cx->lane];
+    tune.skip_trace = facts.all_lead;
+    bool& clean = cx->group_clean[q.part];
     const bool sky_only = tune.sky_mode == 2;       // (touches neither the workspace nor its counters)
     if (!sky_only) clean = false;
-    const hipError_t e = (hipError_t)rtw::launch_render_group(scene->d_scene, fb->accum, fb->argb, cx->d_group_ws[cx->lane], g, tune, cx->stats_enabled,
-                                                              cx->lane ? cx->part_stream[cx->lane] : cx->stream);
+    const hipError_t e = (hipError_t)rtw::launch_render_group(scene->d_scene, fb->accum, fb->argb, cx->d_group_ws[q.part], g, tune, cx->stats_enabled,
+                                                              q.part ? cx->part_stream[q.part] : cx->stream);
     if (e != hipSuccess) return hip_fail(e, "group launch");
     if (sky_only) return RTW_OK;
     clean = true;
     cx->last_pipeline = 4;
-    cx->last_group_passes = cx->lane_count > 1 ? cx->lane_sky_passes : n_passes;
-    if (cx->lane == 0 && !cx->gcounters_pending && g.n_busy > 0 && (!(cx->known_gkey == key) || (cx->hint_tick++ % cx->hint_period) == 0)) {
+    cx->last_group_passes = q.parts > 1 ? q.sky_passes : n_passes;
+    if (q.part == 0 && !cx->gcounters_pending && g.n_busy > 0 && (!(cx->known_gkey == key) || (cx->hint_tick++ % cx->hint_period) == 0)) {
         if (hipMemcpyAsync(cx->h_gcounters, (char*)cx->d_group_ws[0] + 256, 256, hipMemcpyDeviceToHost, cx->stream) == hipSuccess &&
             hipEventRecord(cx->gcounters_event, cx->stream) == hipSuccess) {
             cx->gcounters_pending = true; cx->gcounters_key = key; cx->gcounters_passes = n_passes;
@@ -1615,9 +1677,9 @@ static int render_group(rtw_scene* scene, rtw_framebuffer* fb, RtwRenderParams p
 
 // ---- the hot path -------------------------------------------------------------------------------------------
 // One pass through pipeline 3 (bins + a wave per secondary ray; the one-pass reference of the pass-batched pipeline) or pipeline 0 (one kernel, one
-// thread per pixel: every frame shape and range, the reference-order walk for the work counters).
+// thread per pixel: every frame shape and range, the reference-order walk for the work counters).  pos: where the pass stands in a run of passes.
 static int render_common(rtw_scene* scene, rtw_framebuffer* fb, RtwRenderParams& p, int max_bounce, int use_base_color,
-                         int pass_index, int sub_samples, uint32_t seed)
+                         int pass_index, int sub_samples, uint32_t seed, RunPos pos)
 {
     int rc = check_render_args(scene, fb, max_bounce, pass_index, sub_samples); if (rc != RTW_OK) return rc;
     p.width = fb->width; p.height = fb->height;
@@ -1656,19 +1718,13 @@ static int render_common(rtw_scene* scene, rtw_framebuffer* fb, RtwRenderParams&
         }
         tune.expected_paths = (cx->known_shape == shape) ? cx->known_paths : -1;
         for (int r = 0; r < 32; r++) tune.round_hint[r] = (cx->known_shape == shape) ? cx->known_rounds[r] : -1;
-        tune.aux_stream = cx->aux_stream; tune.fork_event = cx->fork_event; tune.join_event = cx->join_event;
+        set_aux_fork(cx, pos, &tune);
         tune.sky_job0 = sky_job0; tune.gamma_thr = cx->d_gamma;
-        tune.do_fork = cx->batch_pos == 0 || cx->batch_pos == 1 || !cx->aux_unjoined;      // (a run whose earlier passes launched no sky kernel has not forked yet)
-        tune.do_join = cx->batch_pos == 0 || cx->batch_pos == 3; tune.aux_unjoined = &cx->aux_unjoined;
         tune.cu_count = cx->cu_count;
         tune.timing = cx->kernel_timing ? cx->timing_events : nullptr;
-        {   // leading spheres / planes / capsules are tested by the lane that sets a segment up (see RtwRenderParams::lead_shapes)
-            int lead = 0;
-            while (lead < (int)scene->meshes.size() && scene->meshes[(size_t)lead]->kind != RTW_SHAPE_MESH) lead++;
-            p.lead_shapes = lead;
-            tune.has_analytic = scene->has_analytic;
-            tune.skip_trace = lead > 0 && lead == (int)scene->meshes.size();       // nothing is left for the trace kernels
-        }
+        p.lead_shapes = scene->facts.lead_shapes;       // tested by the lane that sets a segment up (see RtwRenderParams::lead_shapes)
+        tune.has_analytic = scene->has_analytic;
+        tune.skip_trace = scene->facts.all_lead;        // nothing is left for the trace kernels
         const size_t coff = layout.counters_off;
         tune.counters_clean = cx->clean_ws == cx->d_workspace && cx->clean_off == coff && cx->d_workspace != nullptr;
         cx->clean_ws = nullptr;
@@ -1690,6 +1746,15 @@ static int render_common(rtw_scene* scene, rtw_framebuffer* fb, RtwRenderParams&
     return RTW_OK;
 }
 
+// a one-pass request for the share `p` (pixels range_begin .. range_end of the frame when ranged)
+static GroupRequest one_pass(const RtwRenderParams& p, bool ranged, int range_begin, int range_end, int max_bounce, int use_base_color, int pass_index, int sub_samples, uint32_t seed)
+{
+    GroupRequest q;
+    q.share = p; q.ranged = ranged; q.range_begin = range_begin; q.range_end = range_end;
+    q.first_pass = pass_index; q.n_passes = 1; q.max_bounce = max_bounce; q.use_base_color = use_base_color; q.sub_samples = sub_samples; q.seed = seed;
+    return q;
+}
+
 int rtw_render_range(rtw_scene* scene, rtw_framebuffer* fb, int begin, int end, int max_bounce, int use_base_color,
                      int pass_index, int sub_samples, uint32_t seed)
 {
@@ -1703,34 +1768,35 @@ int rtw_render_range(rtw_scene* scene, rtw_framebuffer* fb, int begin, int end, 
     if (group_pipeline_ok(scene)) {
         rc = check_render_args(scene, fb, max_bounce, pass_index, sub_samples); if (rc != RTW_OK) return rc;
         if (p.count == 0) return RTW_OK;
-        return render_group(scene, fb, p, !(begin == 0 && end == npix - 1), begin, end, max_bounce, use_base_color, pass_index, 1, sub_samples, seed);
+        bool refused;
+        return render_group(scene, fb, one_pass(p, !(begin == 0 && end == npix - 1), begin, end, max_bounce, use_base_color, pass_index, sub_samples, seed), &refused);
     }
-    return render_common(scene, fb, p, max_bounce, use_base_color, pass_index, sub_samples, seed);
+    return render_common(scene, fb, p, max_bounce, use_base_color, pass_index, sub_samples, seed, RUN_ALONE);
+}
+
+// One pass over this rank's tasks, at `pos` of a run of passes.
+static int render_tasks(rtw_scene* scene, rtw_framebuffer* fb, int task_rows, int rank, int world, int max_bounce, int use_base_color,
+                        int pass_index, int sub_samples, uint32_t seed, RunPos pos)
+{
+    int rc = need_committed(scene); if (rc != RTW_OK) return rc;
+    if (!fb) return fail(RTW_ERR_INVALID, "framebuffer is null");
+    RtwRenderParams p;
+    rc = rank_share(fb, task_rows, rank, world, &p); if (rc != RTW_OK) return rc;
+    if (group_pipeline_ok(scene)) {
+        rc = check_render_args(scene, fb, max_bounce, pass_index, sub_samples); if (rc != RTW_OK) return rc;
+        if (p.count == 0) return RTW_OK;
+        bool refused;
+        GroupRequest q = one_pass(p, false, 0, fb->width * fb->height - 1, max_bounce, use_base_color, pass_index, sub_samples, seed);
+        q.pos = pos;
+        return render_group(scene, fb, q, &refused);
+    }
+    return render_common(scene, fb, p, max_bounce, use_base_color, pass_index, sub_samples, seed, pos);
 }
 
 int rtw_render_tasks(rtw_scene* scene, rtw_framebuffer* fb, int task_rows, int rank, int world, int max_bounce, int use_base_color,
                      int pass_index, int sub_samples, uint32_t seed)
 {
-    int rc = need_committed(scene); if (rc != RTW_OK) return rc;
-    if (!fb) return fail(RTW_ERR_INVALID, "framebuffer is null");
-    if (task_rows < 1 || world < 1 || rank < 0 || rank >= world) return fail(RTW_ERR_INVALID, "bad task partition");
-    RtwRenderParams p; std::memset(&p, 0, sizeof p);
-    const int n_tasks = (fb->height + task_rows - 1) / task_rows;
-    const int mine = n_tasks > rank ? (n_tasks - rank + world - 1) / world : 0;
-    p.begin = 0; p.task_rows = task_rows; p.rank = rank;
-    p.world = world;
-    if (world == 1) { p.count = fb->width * fb->height; }
-    else {
-        const int64_t cnt = (int64_t)mine * task_rows * fb->width;
-        if (cnt > INT32_MAX) return fail(RTW_ERR_LIMIT, "too many work items");
-        p.count = (int)cnt;
-    }
-    if (group_pipeline_ok(scene)) {
-        rc = check_render_args(scene, fb, max_bounce, pass_index, sub_samples); if (rc != RTW_OK) return rc;
-        if (p.count == 0) return RTW_OK;
-        return render_group(scene, fb, p, false, 0, fb->width * fb->height - 1, max_bounce, use_base_color, pass_index, 1, sub_samples, seed);
-    }
-    return render_common(scene, fb, p, max_bounce, use_base_color, pass_index, sub_samples, seed);
+    return render_tasks(scene, fb, task_rows, rank, world, max_bounce, use_base_color, pass_index, sub_samples, seed, RUN_ALONE);
 }
 
 // n_passes accumulated passes (UpdateBitmapPixels' sample loop, Src/RayTracerProgram.cpp:317-361) over this rank's tasks.
@@ -1741,98 +1807,74 @@ int rtw_render_passes(rtw_scene* scene, rtw_framebuffer* fb, int task_rows, int 
     if (!fb) return fail(RTW_ERR_INVALID, "framebuffer is null");
     if (n_passes < 0 || first_pass < 0) return fail(RTW_ERR_INVALID, "bad pass range");
     rtw_context* cx = scene->ctx;
-    if (group_pipeline_ok(scene)) {
-        // groups of passes share one set of launches (rtw_group_kernels.h); the groups of this call fork the second stream once and join it once
-        GroupCall gc;
-        rc = plan_group_call(scene, fb, task_rows, rank, world, max_bounce, first_pass, sub_samples, &gc); if (rc != RTW_OK) return rc;
-        if (gc.p.count == 0) return RTW_OK;
-        const RtwRenderParams& p = gc.p;
-        const long long per_pass = gc.per_pass;
-        const int last_pixel = fb->width * fb->height - 1;
-        cx->group_cap = 0;
-        int done = 0;
-        while (done < n_passes) {
-            int parts = 1;
-            const int k = next_group(cx, per_pass, n_passes - done, max_bounce, scene->texture_carry, use_base_color != 0, &parts);
-            const bool split = parts > 1;
-            rc = RTW_OK;        // (a refused group of the previous round has been re-formed)
-            const bool first = done == 0, last = done + k >= n_passes;
-            cx->batch_pos = (first && last) ? 0 : (first ? 1 : (last ? 3 : 2));
-            if (split) {
-                // The group as `parts` parts on as many streams.  Its kernels are bound by latency, not by a throughput roof: every stage of a
-                // part's chain of launches lasts about as long as its longest ray, whatever the number of rays, so several shorter chains side by side use
-                // the chip where one long chain leaves it idle.  Order kept: a part's share of the sky tiles gets all k passes of its pixels in a row
-                // (first kernel of the part's stream); a part's resolve kernel waits for the previous part's, so a busy tile's passes are added in pass order.
-                const int base = k / parts, rem = k % parts;
-                {   // every part's workspace before anything of the group is launched: a refusal then leaves nothing half done
-                    const size_t need = rtw::group_workspace_bytes(rtw::group_capacity((size_t)per_pass, base + (rem ? 1 : 0)), max_bounce, scene->texture_carry, nullptr);
-                    for (int j = 0; j < parts && rc == RTW_OK; j++) { cx->lane = j; rc = ensure_group_workspace(cx, need); }
-                    cx->lane = 0;
-                }
-                if (rc == RTW_OK) {
-                    (void)hipEventRecord(cx->split_fork, cx->stream);
-                    for (int j = 1; j < parts; j++) (void)hipStreamWaitEvent(cx->part_stream[j], cx->split_fork, 0);
-                    int off = 0;
-                    cx->lane_count = parts; cx->lane_sky_passes = k; cx->lane_sky_first = first_pass + done;
-                    // the sky tiles of the whole group (all k passes of their pixels in a row) FIRST, on the LAST part's stream: that part's chain is enqueued
-                    // last anyway (about 100 us of host time after the first part's), so the sky kernel runs where nothing else would yet.  (Tried: the sky
-                    // kernel on a third, lowest-priority stream -- the last part's first kernel then still starts when the sky kernel ends (the two queues
-                    // share a dispatch pipe), C2 +4 %; every part's first kernel enqueued before any part's remaining launches: no change.)
-                    cx->lane = parts - 1; cx->lane_sky_only = true;
-                    rc = render_group(scene, fb, p, false, 0, last_pixel, max_bounce, use_base_color, first_pass + done, base, sub_samples, seed);
-                    cx->lane_sky_only = false;
-                    for (int j = 0; j < parts && rc == RTW_OK; j++) {
-                        const int kj = base + (j < rem ? 1 : 0);
-                        cx->lane = j;
-                        rc = render_group(scene, fb, p, false, 0, last_pixel, max_bounce, use_base_color, first_pass + done + off, kj, sub_samples, seed);
-                        off += kj;
-                    }
-                    cx->lane = 0; cx->lane_count = 1; cx->lane_sky_passes = 0;
-                    for (int j = 1; j < parts; j++) {
-                        (void)hipEventRecord(cx->part_done[j], cx->part_stream[j]);
-                        (void)hipStreamWaitEvent(cx->stream, cx->part_done[j], 0);
-                    }
-
-                }
-            } else
-                rc = render_group(scene, fb, p, false, 0, last_pixel, max_bounce, use_base_color, first_pass + done, k, sub_samples, seed);
-            cx->batch_pos = 0;
-            if (rc != RTW_OK && cx->ws_refused && k > 1) {
-                // no room for this group's workspace (the context's limit, or the device is full): nothing of the group has been launched -- form smaller
-                // groups for the rest of the call instead of failing (k = 1 needs ~300-600 bytes per path of one pass)
-                cx->ws_refused = false;
-                cx->group_cap = split ? (k + parts - 1) / parts : k / 2;
-                cx->fallbacks++;
-                continue;
-            }
-            if (cx->aux_unjoined && (rc != RTW_OK || last)) {     // the run ends here (an error, or a last group that launched no sky kernel)
-                (void)hipEventRecord(cx->join_event, cx->aux_stream);
-                (void)hipStreamWaitEvent(cx->stream, cx->join_event, 0);
-                cx->aux_unjoined = false;
-            }
-            if (rc != RTW_OK) { cx->group_cap = 0; return rc; }
-            done += k;
+    if (!group_pipeline_ok(scene)) {
+        // pipelines 3 / 0: a pass per set of launches; the passes of this call form a run (the second stream is forked before the first and joined after the last)
+        for (int i = 0; i < n_passes; i++) {
+            const bool last = i + 1 == n_passes;
+            rc = render_tasks(scene, fb, task_rows, rank, world, max_bounce, use_base_color, first_pass + i, sub_samples, seed, run_pos(i == 0, last));
+            if (rc != RTW_OK || last) end_run(cx);
+            if (rc != RTW_OK) return rc;
         }
-        cx->group_cap = 0;
         return RTW_OK;
     }
-    // pipelines 3 / 0: a pass per set of launches; the passes of this call form a run (the second stream is forked before the first and joined after the last)
-    for (int i = 0; i < n_passes; i++) {
-        cx->batch_pos = n_passes == 1 ? 0 : (i + 1 == n_passes ? 3 : (i == 0 ? 1 : 2));
-        rc = rtw_render_tasks(scene, fb, task_rows, rank, world, max_bounce, use_base_color, first_pass + i, sub_samples, seed);
-        cx->batch_pos = 0;
-        if (cx->aux_unjoined && (rc != RTW_OK || i + 1 == n_passes)) {      // the run ends here (an error, or a last pass that launched no sky kernel)
-            (void)hipEventRecord(cx->join_event, cx->aux_stream);
-            (void)hipStreamWaitEvent(cx->stream, cx->join_event, 0);
-            cx->aux_unjoined = false;
+    // groups of passes share one set of launches (rtw_group_kernels.h); the groups of this call fork the second stream once and join it once
+    GroupCall gc;
+    rc = plan_group_call(scene, fb, task_rows, rank, world, max_bounce, first_pass, sub_samples, &gc); if (rc != RTW_OK) return rc;
+    if (gc.p.count == 0) return RTW_OK;
+    GroupRequest q = one_pass(gc.p, false, 0, fb->width * fb->height - 1, max_bounce, use_base_color, first_pass, sub_samples, seed);
+    GroupWalk w{cx, gc.per_pass, n_passes, max_bounce, scene->texture_carry, use_base_color != 0};
+    while (w.next()) {
+        bool refused = false;
+        rc = RTW_OK;
+        q.first_pass = first_pass + w.done; q.n_passes = w.k; q.pos = run_pos(w.first(), w.last());
+        q.part = 0; q.parts = w.parts; q.sky_only = false;
+        if (w.parts > 1) {
+            // The group as `parts` parts on as many streams.  Its kernels are bound by latency, not by a throughput roof: every stage of a
+            // part's chain of launches lasts about as long as its longest ray, whatever the number of rays, so several shorter chains side by side use
+            // the chip where one long chain leaves it idle.  Order kept: a part's share of the sky tiles gets all k passes of its pixels in a row
+            // (first kernel of the part's stream); a part's resolve kernel waits for the previous part's, so a busy tile's passes are added in pass order.
+            // Every part's workspace before anything of the group is launched: a refusal then leaves nothing half done.
+            for (int j = 0; j < w.parts && rc == RTW_OK; j++) rc = ensure_group_workspace(cx, j, w.part_bytes(), false, &refused);
+            if (rc == RTW_OK) {
+                (void)hipEventRecord(cx->split_fork, cx->stream);
+                for (int j = 1; j < w.parts; j++) (void)hipStreamWaitEvent(cx->part_stream[j], cx->split_fork, 0);
+                q.sky_first = q.first_pass; q.sky_passes = w.k;
+                // the sky tiles of the whole group (all k passes of their pixels in a row) FIRST, on the LAST part's stream: that part's chain is enqueued
+                // last anyway (about 100 us of host time after the first part's), so the sky kernel runs where nothing else would yet.  (Tried: the sky
+                // kernel on a third, lowest-priority stream -- the last part's first kernel then still starts when the sky kernel ends (the two queues
+                // share a dispatch pipe), C2 +4 %; every part's first kernel enqueued before any part's remaining launches: no change.)
+                q.part = w.parts - 1; q.n_passes = w.k / w.parts; q.sky_only = true;
+                rc = render_group(scene, fb, q, &refused);
+                q.sky_only = false;
+                for (int j = 0; j < w.parts && rc == RTW_OK; j++) {
+                    q.part = j; q.n_passes = w.part_passes(j);
+                    rc = render_group(scene, fb, q, &refused);
+                    q.first_pass += q.n_passes;
+                }
+                for (int j = 1; j < w.parts; j++) {
+                    (void)hipEventRecord(cx->part_done[j], cx->part_stream[j]);
+                    (void)hipStreamWaitEvent(cx->stream, cx->part_done[j], 0);
+                }
+            }
+        } else
+            rc = render_group(scene, fb, q, &refused);
+        if (rc != RTW_OK && refused && w.k > 1) {
+            // no room for this group's workspace (the context's limit, or the device is full): nothing of the group has been launched -- form smaller
+            // groups for the rest of the call instead of failing (k = 1 needs ~300-600 bytes per path of one pass)
+            w.cap = w.parts > 1 ? (w.k + w.parts - 1) / w.parts : w.k / 2;
+            cx->fallbacks++;
+            continue;
         }
+        if (rc != RTW_OK || w.last()) end_run(cx);
         if (rc != RTW_OK) return rc;
+        w.done += w.k;
     }
     return RTW_OK;
 }
 
 // Everything a later rtw_render_passes call with these arguments needs that would otherwise be made inside it: the screen bins and tile tables of this
-// frame shape and the group workspace(s) of the largest group that call will form.  Renders nothing.
+// frame shape and the group workspace(s) of the largest group that call will form (planned as a full render, whatever cap a refusal may later set).
+// Renders nothing.
 int rtw_render_reserve(rtw_scene* scene, rtw_framebuffer* fb, int task_rows, int rank, int world, int max_bounce, int n_passes, int sub_samples)
 {
     int rc = need_committed(scene); if (rc != RTW_OK) return rc;
@@ -1846,19 +1888,11 @@ int rtw_render_reserve(rtw_scene* scene, rtw_framebuffer* fb, int task_rows, int
     RtwRenderParams t = gc.p; t.width = fb->width; t.height = fb->height;
     if (!choose_group_tiles(t, 0, fb->width * fb->height - 1)) return fail(RTW_ERR_LIMIT, "frame too large for the tile mapping");
     size_t need[RTW_MAX_PARTS] = { 0, 0, 0, 0 };
-    const int saved_cap = cx->group_cap;
-    cx->group_cap = 0;
-    for (int done = 0; done < n_passes;) {
-        int parts = 1;
-        const int k = next_group(cx, gc.per_pass, n_passes - done, max_bounce, scene->texture_carry, false, &parts);
-        const int kk = (k + parts - 1) / parts;
-        const size_t b = rtw::group_workspace_bytes(rtw::group_capacity((size_t)gc.per_pass, kk), max_bounce, scene->texture_carry, nullptr);
-        for (int j = 0; j < parts; j++) if (b > need[j]) need[j] = b;
-        done += k;
-    }
-    cx->group_cap = saved_cap;
+    for (GroupWalk w{cx, gc.per_pass, n_passes, max_bounce, scene->texture_carry, false}; w.next(); w.done += w.k)
+        for (int j = 0; j < w.parts; j++) need[j] = std::max(need[j], w.part_bytes());
+    bool refused = false;
     for (int j = 0; j < RTW_MAX_PARTS && rc == RTW_OK; j++) if (need[j] > 0) {
-        cx->lane = j; rc = ensure_group_workspace(cx, need[j]);
+        rc = ensure_group_workspace(cx, j, need[j], false, &refused);
         // ... and the part's list counters zeroed on the part's own stream: its first group needs no memset, and a stream's first operation (the runtime
         // sets its hardware queue up then) does not fall into a timed call
         if (rc == RTW_OK && !cx->group_clean[j]) {
@@ -1866,10 +1900,10 @@ int rtw_render_reserve(rtw_scene* scene, rtw_framebuffer* fb, int task_rows, int
             if (hipMemsetAsync(cx->d_group_ws[j], 0, 256, ps) == hipSuccess && hipStreamSynchronize(ps) == hipSuccess) cx->group_clean[j] = true;
         }
     }
-    cx->lane = 0;
-    if (rc != RTW_OK && cx->ws_refused) { cx->ws_refused = false; return RTW_OK; }      // not an error: the call will form smaller groups
+    if (rc != RTW_OK && refused) return RTW_OK;     // not an error: the call will form smaller groups
     return rc;
 }
+
 
 // device memory this context holds right now: the group workspaces, the older pipelines' workspace and its share of the unit-vector table
 // (201 MB per device, shared by the contexts on it); scenes and framebuffers are the caller's objects and not counted
