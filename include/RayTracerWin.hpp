@@ -290,6 +290,14 @@ public:
         RtwCheck(rtw_scene_set_camera(Scene, &cam));
     }
     rtw_camera GetCamera() const { rtw_camera cam; RtwCheck(rtw_scene_get_camera(Scene, &cam)); return cam; }
+    // Depth of field: a thin lens of this radius at the eye, focused on the plane focusDistance along the viewing direction (world units);
+    // radius 0 is the pinhole (the default).  Before or after the first render, and between render calls.
+    void SetLens(float radius, float focusDistance)
+    {
+        const rtw_lens lens = { radius, focusDistance };
+        RtwCheck(rtw_scene_set_lens(Scene, &lens));
+    }
+    rtw_lens GetLens() const { rtw_lens lens; RtwCheck(rtw_scene_get_lens(Scene, &lens)); return lens; }
     void Commit() { if (!Committed) { RtwCheck(rtw_scene_commit(Scene)); Committed = true; } }
     rtw_scene* Get() { Commit(); return Scene; }
 private:

@@ -104,7 +104,11 @@ int rtw_context_synchronize(rtw_context* ctx);
  *                   shape >= 0 becomes the byte) -- the A/B baseline and cross-check; -1 = the measured rule (profiles/query_experiments.md): any-hit on
  *                   one-mesh scenes runs the query kernel, everything else the old one.  Results never depend on it, nor on the next;
  *   "query_blocks"  (0 = one grid sized from the device's compute units) > 0: at most exactly that many blocks, so that few rays make many trips of
- *                   the query kernel's batch loop. */
+ *                   the query kernel's batch loop;
+ *   "lens_route"    (-1) pipeline 4, scenes with a lens (rtw_scene_set_lens): 1 = the camera round -- glens_kernel makes the lens rays, a lane per path, and
+ *                   the ray-per-lane trace kernels of the bounce rounds find their hits in a round of its own ahead of round 0; 0 = gprimary_kernel's LENS
+ *                   instantiation, which walks the trees itself a tile per wave; -1 = the measured rule (profiles/lens_experiments.md): route 0, which
+ *                   won on every scene measured -- the camera round is kept as the cross-check.  Results never depend on it. */
 int rtw_context_set_option(rtw_context* ctx, const char* name, int value);
 /* with option "kernel_timing" = 1: HIP-event durations (ms) of the latest pass's three stages -- primary kernel(s),
  * the per-bounce trace / shade launches, resolve -- measured on the context's stream; waits for that pass. */
@@ -191,6 +195,31 @@ int rtw_scene_get_camera(const rtw_scene* scene, rtw_camera* out);
  * direction, distance), the layout rtw_trace_closest / rtw_ray_trace take.  Host only, needs no context. */
 int rtw_camera_rays(const rtw_camera* cam, int width, int height, const int32_t* pixels, int64_t n,
                     int pass_index, int sub_sample, uint32_t seed, float* rays7);
+
+/* ---- thin lens: depth of field ----
+ * A lens of radius aperture_radius (world units) at the eye, in the plane of `right` and `up`, focused on the plane focus_distance along `forward`:
+ * a point of that plane is sharp, everything else is blurred by its circle of confusion.  aperture_radius == 0 is the pinhole exactly: the same
+ * kernel instantiations, the same screen bins, the same images bit for bit.  For aperture_radius > 0 a sample's ray is (float32, every product and
+ * every sum rounded on its own):
+ *   1. a = dx + ox, b = dy + oy and v[k] as for the camera above, jitter draws (counters 0 and 1 of the path's stream) included; the path's counter
+ *      stands at 2 afterwards, with or without a lens, so no later random decision of any path changes.
+ *   2. the lens point from a stream of its own, key_l = stream_key(seed, pixel, (pass_index * 4 + sub_sample) | 0x80000000u): for try t = 0 .. 7
+ *      lx = 2 u(2t) - 1, ly = 2 u(2t + 1) - 1 with u(c) = (float)(int32)(mix32(key_l + c) >> 1) / 2147483648.0f; the first try with
+ *      lx * lx + ly * ly <= 1.0f is taken; if none of the eight is (4.5e-6 of the samples), lx = ly = 0.
+ *      pass_index must stay below 2^29 with a lens (RTW_ERR_LIMIT above): bit 31 of the sample word belongs to the lens stream.
+ *   3. s = focus_distance / focal;  lxr = lx * aperture_radius, lyr = ly * aperture_radius;  off[k] = right[k] * lxr + up[k] * lyr;
+ *      origin[k] = eye[k] + off[k];  w[k] = v[k] * s - off[k];  dir = w * (1.0f / sqrtf((w.x * w.x + w.y * w.y) + w.z * w.z)),  distance 1000.
+ * With a lens no mesh gets screen bins (the projection from `eye` no longer bounds what a tile's rays can meet: rtw_scene_mesh_bins returns 0),
+ * every tile is rendered as a busy one, and the workspace of the pass-batched pipeline is sized for all pixels of the frame. */
+typedef struct { float aperture_radius; float focus_distance; } rtw_lens;   /* world units; focus_distance measured along `forward` */
+/* The lens every render call of this scene uses from now on (NULL or aperture_radius == 0: the pinhole).  Before or after commit and between render
+ * calls, like rtw_scene_set_camera: after commit it waits for the context's streams and drops the scene's cached screen bins and tile tables.
+ * RTW_ERR_INVALID for a non-finite value, aperture_radius < 0 or focus_distance <= 0. */
+int rtw_scene_set_lens(rtw_scene* scene, const rtw_lens* lens);
+int rtw_scene_get_lens(const rtw_scene* scene, rtw_lens* out);
+/* rtw_camera_rays through a lens (NULL or aperture_radius == 0: rtw_camera_rays bit for bit).  Host only, needs no context. */
+int rtw_lens_rays(const rtw_camera* cam, const rtw_lens* lens, int width, int height, const int32_t* pixels, int64_t n,
+                  int pass_index, int sub_sample, uint32_t seed, float* rays7);
 
 /* Screen-space bins of the scene's current camera (the reference's: Src/RayTracerProgram.cpp:133-165) for a
  * width x height frame cut into bin_w x bin_h pixel bins: CSR offsets (bins + 1) and, per bin, the

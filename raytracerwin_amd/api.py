@@ -452,6 +452,32 @@ def camera_rays(camera, width, height, pixels, pass_index=0, sub_sample=0, seed=
     return rays
 
 
+class Lens(C.Structure):
+    """rtw_lens: a thin lens of radius aperture_radius at the eye, focused on the plane focus_distance along the camera's `forward`
+    (world units).  aperture_radius 0 is the pinhole."""
+    _fields_ = [("aperture_radius", C.c_float), ("focus_distance", C.c_float)]
+
+    def __init__(self, aperture_radius=0.0, focus_distance=1.0):
+        super().__init__(float(aperture_radius), float(focus_distance))
+
+    def __eq__(self, other):
+        return isinstance(other, Lens) and bytes(self) == bytes(other)
+
+    __hash__ = None
+
+    def __repr__(self):
+        return "Lens(aperture_radius=%r, focus_distance=%r)" % (self.aperture_radius, self.focus_distance)
+
+
+def lens_rays(camera, lens, width, height, pixels, pass_index=0, sub_sample=0, seed=12345):
+    """camera_rays through a lens (None or aperture_radius 0: camera_rays bit for bit): (n, 7) origin, direction, distance.  Host only."""
+    px = np.ascontiguousarray(pixels, np.int32).reshape(-1)
+    rays = np.zeros((len(px), 7), np.float32)
+    _check(library().rtw_lens_rays(None if camera is None else C.byref(camera), None if lens is None else C.byref(lens), int(width), int(height),
+                                   _p(px), C.c_int64(len(px)), int(pass_index), int(sub_sample), C.c_uint32(seed), _p(rays)))
+    return rays
+
+
 class RayTracerScene:
     """Src/RayTracerScene.h:43-62.  AddShape() collects shapes; the first query commits."""
 
@@ -513,6 +539,15 @@ class RayTracerScene:
         cam = Camera()
         _check(library().rtw_scene_get_camera(self.h, C.byref(cam)))
         return cam
+
+    def set_lens(self, lens=None):
+        """The lens of every later render call (None or aperture_radius 0 = the pinhole); before or after commit, and between render calls."""
+        _check(library().rtw_scene_set_lens(self.h, None if lens is None else C.byref(lens)))
+
+    def get_lens(self):
+        lens = Lens()
+        _check(library().rtw_scene_get_lens(self.h, C.byref(lens)))
+        return lens
 
     def commit(self):
         if not self.committed:

@@ -69,6 +69,8 @@ struct GroupTuning : AuxFork {      // (the sky-only tiles run on aux_stream bes
     bool skip_trace = false;                 // every shape is a leading analytic shape: the shading lanes do the whole query, no trace launches
     int overflow_hint[32];                   // how many rays that were in the previous group, per round (-1 = unknown)
     int wave_below = 0;                      // a trace round whose list (previous group's length) is shorter than this runs a wave per ray
+    bool camera_round = false;               // a lens (rp.lens): glens_kernel makes the camera rays and the trace kernels find their hits in a round of its own
+                                             // ahead of the bounce rounds; false: gprimary_kernel's LENS instantiation walks the trees itself (option "lens_route")
     hipEvent_t* timing = nullptr;  // null, or 4 events: before the primary kernel, after it, after the bounce rounds, after resolve
 };
 int launch_render_group(const RtwSceneDev* sc, void* accum, void* argb, void* workspace, const RtwGroupParams& g, const GroupTuning& tune, bool stats, hipStream_t stream);

@@ -767,26 +767,61 @@ __device__ f3 trace_path(const RtwSceneDev* __restrict__ sc, const TravCtx& tc, 
 // CAM = false: the reference's fixed camera as constants (the code every default-pose frame has always run);
 // CAM = true: the scene's camera from the launch parameters (rtw_types.h RtwCamera: every product and every sum rounded on its own)
 template <bool CAM>
-__device__ __forceinline__ Ray camera_ray_from(const RtwCamera& c, float a, float b)
+__device__ __forceinline__ f3 camera_view(const RtwCamera& c, float a, float b)        // v of rtw_types.h RtwCamera, before it is normalised
 {
-    Ray r;
-    if (CAM) {
-        r.o = mk(c.eye[0], c.eye[1], c.eye[2]);
-        r.d = normalized(mk((c.right[0] * a + c.up[0] * b) + c.forward[0] * c.focal,
-                            (c.right[1] * a + c.up[1] * b) + c.forward[1] * c.focal,
-                            (c.right[2] * a + c.up[2] * b) + c.forward[2] * c.focal));
-    } else {
-        r.o = mk(0, 0, 7.0f);
-        r.d = normalized(mk(a, b, -0.5f));
-    }
-    r.dist = 1000.0f;
-    return r;
+    if (CAM) return mk((c.right[0] * a + c.up[0] * b) + c.forward[0] * c.focal,
+                       (c.right[1] * a + c.up[1] * b) + c.forward[1] * c.focal,
+                       (c.right[2] * a + c.up[2] * b) + c.forward[2] * c.focal);
+    return mk(a, b, -0.5f);
 }
 template <bool CAM>
 __device__ __forceinline__ f3 camera_eye(const RtwCamera& c) { return CAM ? mk(c.eye[0], c.eye[1], c.eye[2]) : mk(0, 0, 7.0f); }
-
 template <bool CAM>
-__device__ __forceinline__ Ray camera_ray(const RtwRenderParams& p, int pixel, int i, PathRng& rng)
+__device__ __forceinline__ Ray camera_ray_from(const RtwCamera& c, float a, float b)
+{
+    Ray r;
+    r.o = camera_eye<CAM>(c);
+    r.d = normalized(camera_view<CAM>(c, a, b));
+    r.dist = 1000.0f;
+    return r;
+}
+
+// ---- the thin lens (rtw_lens of rtwin.h) ----
+// The point on the unit disc: rejection sampling, at most eight tries, from a stream of its own -- key_l = stream_key(seed, pixel,
+// (pass * 4 + sub) | RTW_LENS_STREAM), try t reads counters 2 t and 2 t + 1 -- so the path's own stream stands at counter 2 after the camera
+// ray with or without a lens.  No try inside the disc (4.5e-6 of the samples): the centre.
+__device__ __forceinline__ float lens_uniform(uint32_t key_l, uint32_t c) { return (float)(int32_t)(mix32(key_l + c) >> 1) / 2147483648.0f; }
+__device__ __forceinline__ void lens_point(uint32_t key_l, float& lx, float& ly)
+{
+    lx = 0.0f; ly = 0.0f;
+    for (uint32_t t = 0; t < 8u; t++) {
+        const float x = 2.0f * lens_uniform(key_l, 2u * t) - 1.0f, y = 2.0f * lens_uniform(key_l, 2u * t + 1u) - 1.0f;
+        if (x * x + y * y <= 1.0f) { lx = x; ly = y; break; }
+    }
+}
+// The ray through the point focus_distance along `forward` that the pinhole ray of (a, b) meets, from the lens point: every product and every
+// sum rounded on its own (include/rtwin.h spells the steps out; rtw_lens_rays and the tests' NumPy model repeat them).
+__device__ __forceinline__ Ray lens_ray_from(const RtwRenderParams& p, float a, float b, uint32_t key_l)
+{
+    const RtwCamera& c = p.cam;
+    const f3 v = camera_view<true>(c, a, b);
+    float lx, ly;
+    lens_point(key_l, lx, ly);
+    const float s = p.lens_focus / c.focal;
+    const float lxr = lx * p.lens_radius, lyr = ly * p.lens_radius;
+    const f3 off = mk(c.right[0] * lxr + c.up[0] * lyr, c.right[1] * lxr + c.up[1] * lyr, c.right[2] * lxr + c.up[2] * lyr);
+    const f3 w = mk(v.x * s - off.x, v.y * s - off.y, v.z * s - off.z);
+    const float inv = 1.0f / sqrtf((w.x * w.x + w.y * w.y) + w.z * w.z);
+    Ray r;
+    r.o = mk(c.eye[0] + off.x, c.eye[1] + off.y, c.eye[2] + off.z);
+    r.d = mk(w.x * inv, w.y * inv, w.z * inv);
+    r.dist = 1000.0f;
+    return r;
+}
+
+// `pass`: the pass the sample belongs to (the lens stream's key needs it; unused without a lens)
+template <bool CAM, bool LENS = false>
+__device__ __forceinline__ Ray camera_ray(const RtwRenderParams& p, int pixel, int i, PathRng& rng, uint32_t pass = 0u)
 {
     const int width = p.width, height = p.height;
     const float aspect = (float)width / (float)height;
@@ -799,12 +834,13 @@ __device__ __forceinline__ Ray camera_ray(const RtwRenderParams& p, int pixel, i
     float oy = (i & 2) ? inv_pixel_radius : 0.0f;
     ox += (rng.random() - 0.5f) * offset_radius;
     oy += (rng.random() - 0.5f) * offset_radius;
+    if (LENS) return lens_ray_from(p, dx + ox, dy + oy, stream_key(p.seed, (uint32_t)pixel, (pass * 4u + (uint32_t)i) | RTW_LENS_STREAM));
     return camera_ray_from<CAM>(p.cam, dx + ox, dy + oy);
 }
 
 // the same ray from the host's per-column / per-row tables (tiled pipelines): dx and dy hold exactly the floats above
-template <bool CAM>
-__device__ __forceinline__ Ray camera_ray_xy(const RtwRenderParams& p, int x, int y, int i, PathRng& rng)
+template <bool CAM, bool LENS = false>
+__device__ __forceinline__ Ray camera_ray_xy(const RtwRenderParams& p, int x, int y, int i, PathRng& rng, uint32_t pass = 0u)
 {
     const float dx = p.cam_dx[x], dy = p.cam_dy[y];
     const float inv_pixel_radius = 1.0f / (p.width * 4);
@@ -813,6 +849,7 @@ __device__ __forceinline__ Ray camera_ray_xy(const RtwRenderParams& p, int x, in
     float oy = (i & 2) ? inv_pixel_radius : 0.0f;
     ox += (rng.random() - 0.5f) * offset_radius;
     oy += (rng.random() - 0.5f) * offset_radius;
+    if (LENS) return lens_ray_from(p, dx + ox, dy + oy, stream_key(p.seed, (uint32_t)(y * p.width + x), (pass * 4u + (uint32_t)i) | RTW_LENS_STREAM));
     return camera_ray_from<CAM>(p.cam, dx + ox, dy + oy);
 }
 
@@ -917,7 +954,7 @@ __device__ __forceinline__ int work_to_pixel(const RtwRenderParams& p, int wi)
 }
 
 // ---- kernels -----------------------------------------------------------------------------------------
-template <bool STATS, bool CAM>
+template <bool STATS, bool CAM, bool LENS = false>
 __global__ __launch_bounds__(256) void render_kernel(const RtwSceneDev* __restrict__ sc, float4* __restrict__ accum,
                                                      uint32_t* __restrict__ argb, float4* __restrict__ ws, RtwRenderParams p)
 {
@@ -935,7 +972,7 @@ __global__ __launch_bounds__(256) void render_kernel(const RtwSceneDev* __restri
         f3 c = mk(0, 0, 0);
         for (int i = 0; i < p.sub_samples; i++) {
             PathRng rng; rng_init(rng, p.seed, phase, (uint64_t)npix, (uint32_t)pixel, (uint32_t)p.pass_index, (uint32_t)i);
-            const Ray ray = camera_ray<CAM>(p, pixel, i, rng);
+            const Ray ray = camera_ray<CAM, LENS>(p, pixel, i, rng, (uint32_t)p.pass_index);
             if (STATS) ct.cams++;
             c = c + trace_path<STATS>(sc, tc, ray, p.max_bounce, p.preview != 0, rng, ct, lv);
         }
@@ -1260,6 +1297,7 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(GatherPlan g)
 template <typename F> void with_flags(bool a, F&& f) { if (a) f(std::true_type{}); else f(std::false_type{}); }
 template <typename F> void with_flags(bool a, bool b, F&& f) { with_flags(a, [&](auto A) { with_flags(b, [&](auto B) { f(A, B); }); }); }
 template <typename F> void with_flags(bool a, bool b, bool c, F&& f) { with_flags(a, [&](auto A) { with_flags(b, c, [&](auto B, auto C) { f(A, B, C); }); }); }
+template <typename F> void with_flags(bool a, bool b, bool c, bool d, F&& f) { with_flags(a, [&](auto A) { with_flags(b, c, d, [&](auto B, auto C, auto D) { f(A, B, C, D); }); }); }
 // The three block shapes of the ray-per-lane trace kernels (gtrace_kernel, qtrace_kernel): 1024 threads with a tree's upper levels staged in LDS
 // (STG 1) or its whole tree (STG 2), 256 threads with nothing staged (STG 0).  lds(top): candidate lists + `top` staged records.
 template <int NT_, int CAP_, int STG_> struct TraceShape {
@@ -1324,8 +1362,9 @@ int launch_render(const RtwSceneDev* sc, void* accum, void* argb, void* ws, cons
     if (p.count <= 0) return 0;
     const int block = 256;
     const int grid = (p.count + block - 1) / block;
-    with_flags(stats, p.cam_general != 0, [&](auto ST, auto CAM) {
-        launch(render_kernel<decltype(ST)::value, decltype(CAM)::value>, dim3(grid), dim3(block), 0, stream, sc, (float4*)accum, (uint32_t*)argb, (float4*)ws, p);
+    with_flags(stats, p.cam_general != 0, p.lens != 0, [&](auto ST, auto CAM, auto LENS) {     // (a lens implies the general camera)
+        constexpr bool lens = decltype(LENS)::value, cam = decltype(CAM)::value || lens;
+        launch(render_kernel<decltype(ST)::value, cam, lens>, dim3(grid), dim3(block), 0, stream, sc, (float4*)accum, (uint32_t*)argb, (float4*)ws, p);
     });
     return (int)hipGetLastError();
 }
@@ -1390,8 +1429,9 @@ int launch_render_pipeline(const RtwSceneDev* sc, void* accum, void* argb, void*
         }
         const int jobs_grid = ph.tile_order ? (ph.n_jobs + 3) / 4 : grid;        // a wave per job (a tile, or a tile's sub-sample); else waves take jobs in turn
         const int pgrid = jobs_grid < tune.cu_count * 64 ? jobs_grid : tune.cu_count * 64;
-        with_flags(stats, tune.has_analytic, p.cam_general != 0, [&](auto ST, auto AN, auto CAM) {
-            launch(primary_bins_kernel<decltype(ST)::value, decltype(AN)::value, decltype(CAM)::value>, dim3(pgrid), dim3(block), 0, stream, sc, (float4*)accum, (uint32_t*)argb, pb, ph);
+        with_flags(stats, tune.has_analytic, p.cam_general != 0, p.lens != 0, [&](auto ST, auto AN, auto CAM, auto LENS) {
+            constexpr bool lens = decltype(LENS)::value, cam = decltype(CAM)::value || lens;
+            launch(primary_bins_kernel<decltype(ST)::value, decltype(AN)::value, cam, lens>, dim3(pgrid), dim3(block), 0, stream, sc, (float4*)accum, (uint32_t*)argb, pb, ph);
         });
     }
     if (tune.timing) (void)hipEventRecord(tune.timing[1], stream);
@@ -1480,19 +1520,31 @@ int launch_render_group(const RtwSceneDev* sc, void* accum, void* argb, void* wo
     if (tune.timing) (void)hipEventRecord(tune.timing[0], stream);
     if (g.n_busy > 0) {
         const long long live_paths = (long long)g.n_busy * 64 * p.sub_samples * g.n_passes;
-        {
+        const bool camera_round = p.lens != 0 && tune.camera_round;
+        if (camera_round) {
+            // a lens, the camera round: glens_kernel only makes the rays (a wave per job and pass); trace(0) finds their hits and shade(1) is the first
+            // per-hit block, so every round below is one later than without a lens
+            const unsigned pgrid = (unsigned)(((long long)g.n_jobs * g.n_passes + 3) / 4);
+            with_flags(stats, tune.has_analytic, [&](auto ST, auto AN) {
+                launch(glens_kernel<decltype(ST)::value, decltype(AN)::value>, dim3(pgrid), dim3(256), 0, stream, sc, gb, g);
+            });
+        } else {
             const int ppw = (g.primary_passes > 1 && g.primary_passes * p.sub_samples <= 4) ? g.primary_passes : 1;        // as the kernel reads it
             const long long waves = (long long)g.n_jobs * ((g.n_passes + ppw - 1) / ppw);
             const unsigned pgrid = (unsigned)((waves + 3) / 4);
-            with_flags(stats, tune.has_analytic, p.cam_general != 0, [&](auto ST, auto AN, auto CAM) {
-                launch(gprimary_kernel<decltype(ST)::value, decltype(AN)::value, decltype(CAM)::value>, dim3(pgrid), dim3(256), 0, stream, sc, gb, g);
+            with_flags(stats, tune.has_analytic, p.cam_general != 0, p.lens != 0, [&](auto ST, auto AN, auto CAM, auto LENS) {
+                constexpr bool lens = decltype(LENS)::value, cam = decltype(CAM)::value || lens;
+                launch(gprimary_kernel<decltype(ST)::value, decltype(AN)::value, cam, lens>, dim3(pgrid), dim3(256), 0, stream, sc, gb, g);
             });
         }
         if (tune.timing) (void)hipEventRecord(tune.timing[1], stream);
         constexpr int NTV = 128;            // wave-per-ray launches: 128-thread blocks, a wave takes rays in turn
         const size_t wave_lds = (size_t)(NTV / 64) * RTW_WAVE_LDS_WORDS * 4;
         const long long wave_cap = (long long)tune.cu_count * 64;
-        for (int r = 1; r < p.max_bounce && !p.preview; r++) {      // the primary kernel was shade(0); trace(r - 1) then shade(r)
+        // the primary kernel was shade(0): rounds 1 .. max_bounce - 1 (none for a preview); after the camera round nothing is shaded yet: rounds 1 .. max_bounce
+        // (a preview ends at its first hit: round 1)
+        const int last_round = camera_round ? (p.max_bounce == 0 ? 0 : (p.preview ? 1 : p.max_bounce)) : (p.preview ? 0 : p.max_bounce - 1);
+        for (int r = 1; r <= last_round; r++) {      // trace(r - 1) then shade(r)
             // blocks of 256 lanes (a grid-stride loop takes any excess) for the round's whole list (the shade launch) ...
             const unsigned sb_full = blocks_from_hint(tune.round_hint[r - 1], 1024, 256, 65536, live_paths);
             // ... and for the rays the trace launch takes: the whole list, or (leading analytic shapes) the part the shading lanes could not finish

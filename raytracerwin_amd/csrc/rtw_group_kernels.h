@@ -12,6 +12,8 @@
 //   gprimary_kernel  one wave per (busy tile, pass[, sub-sample]): the camera rays through the tile's screen bin -- the bins walk of
 //                    primary_bins_kernel -- and the first shading step.  A path that ends writes its radiance, one that goes on saves
 //                    its state in its slot and joins round 0's ray list (ONE atomic per wave).
+//   glens_kernel     scenes with a thin lens, option "lens_route" 1: instead of gprimary_kernel, a lane per path only MAKES the lens ray and queues it;
+//                    the trace / shade kernels below then run one more round, the camera round, ahead of the bounce rounds.
 //   gtrace_kernel    ONE LANE PER RAY over the reference's own binary tree in preorder (skip links, no stack): with K passes in one
 //                    launch there are enough rays to fill the chip a ray per lane, and a lane's node visit costs ~30 instructions
 //                    where a whole wave per ray spent ~450 per ray on mostly idle lanes.  Leaves whose box is hit are only NOTED
@@ -327,7 +329,7 @@ __device__ __forceinline__ void bins_walk_rays(const RtwShapeDev& sh, const uint
 
 __device__ __forceinline__ float pick4(int r, float a, float b, float c, float d) { return r == 0 ? a : (r == 1 ? b : (r == 2 ? c : d)); }
 
-template <bool STATS, bool AN, bool CAM>
+template <bool STATS, bool AN, bool CAM, bool LENS = false>
 #ifndef RTW_GPRIMARY_MINB
 #define RTW_GPRIMARY_MINB 3      // measured in one session: 3 blocks of 256 per CU (<= 168 VGPRs) makes the primary kernel 13 % faster on unitychan (C4 0.343 -> 0.315 ms per pass), neutral on TorusKnot; 4 blocks (round 3, 128 VGPRs): C2 +3 %, C3 +4 % slower
 #endif
@@ -379,7 +381,7 @@ __global__ __launch_bounds__(256, RTW_GPRIMARY_MINB) void gprimary_kernel(const 
 #pragma unroll
         for (int r = 0; r < 4; r++) w_pos[r] = mk(0, 0, 0);
         bool shared_walk = false;
-        if (!AN && g.primary_passes > 0 && n_shapes == 1 && nr > 1 && nr <= 4 && near_wave && p.max_bounce != 0 && p.bins[0].off != nullptr) {
+        if (!LENS && !AN && g.primary_passes > 0 && n_shapes == 1 && nr > 1 && nr <= 4 && near_wave && p.max_bounce != 0 && p.bins[0].off != nullptr) {
             f3 w_d[4]; bool w_act[4]; bool all_tame = true;
             const RtwShapeDev& sh = sc->shapes[0];
 #pragma unroll
@@ -406,7 +408,7 @@ __global__ __launch_bounds__(256, RTW_GPRIMARY_MINB) void gprimary_kernel(const 
             const int i = only_sample >= 0 ? only_sample : (int)((uint32_t)r - po * nsub);
             const int pass = g.first_pass + (int)kpass;
             PathRng rng; rng_init(rng, p.seed, phase, (uint64_t)npix, (uint32_t)pixel, (uint32_t)pass, (uint32_t)i);
-            const Ray ray = camera_ray_xy<CAM>(p, px, py, i, rng);
+            const Ray ray = camera_ray_xy<CAM, LENS>(p, px, py, i, rng, (uint32_t)pass);
             if (STATS && live) ct.cams++;
             const uint32_t slot = group_slot(g, b, (uint32_t)lane, (uint32_t)i, kpass);
             f3 si = mk(0, 0, 0);
@@ -552,6 +554,74 @@ __global__ __launch_bounds__(256, RTW_GPRIMARY_MINB) void gprimary_kernel(const 
         const uint32_t c0 = (uint32_t)__popcll(m0), c1 = (uint32_t)__popcll(m1), c2 = (uint32_t)__popcll(m2), c3 = (uint32_t)__popcll(m3);
         const uint32_t qb = block_reserve<4>(&gb.counters[0], c0 + c1 + c2 + c3, part);
         auto slot_of = [&](uint32_t r) { const uint32_t po = r / nsub; return group_slot(g, b, (uint32_t)lane, nsub == 1u ? sub0 : r - po * nsub, kbase + po); };
+        if (queued & 1u) gb.list0[qb + (uint32_t)mbcnt(m0)] = slot_of(0u);
+        if (queued & 2u) gb.list0[qb + c0 + (uint32_t)mbcnt(m1)] = slot_of(1u);
+        if (queued & 4u) gb.list0[qb + c0 + c1 + (uint32_t)mbcnt(m2)] = slot_of(2u);
+        if (queued & 8u) gb.list0[qb + c0 + c1 + c2 + (uint32_t)mbcnt(m3)] = slot_of(3u);
+        if (AN && p.lead_shapes > 0) {       // the subset that still has to be traced
+            for (uint32_t r = 0; r < 4u; r++)
+                block_push<4>(gb.tlist0, &gb.counters[24], (tqueued >> r) & 1u, slot_of(r), part);
+        }
+    }
+    if (STATS) flush_counters(sc, ct);
+}
+
+// ---- camera rays through a thin lens: the camera round ------------------------------------------------------------------------------
+// With a lens (RtwRenderParams::lens) every camera ray has its own origin: no screen bins, no shared walk, primary visibility is a general ray
+// query -- the kind the trace kernels below answer a ray per lane.  This kernel only MAKES the rays: one wave per (job, pass) in the primary
+// kernel's job order (a tile's paths stay neighbours in the list), a lane per pixel, a ray per sub-sample of the job.  A lane saves the path's
+// state in its slot (full depth, no level yet, the path's stream at counter 2) and the slot joins the list of the camera round, which the host
+// runs as round 0 ahead of the bounce rounds: trace(0) finds the camera ray's hit, gshade_kernel(1) is RayTrace's first per-hit block (sky for
+// a miss), and so on -- every round one later than without a lens, max_bounce shade rounds in all.  One slot write per lane, ONE atomic per block.
+template <bool STATS, bool AN>
+__global__ __launch_bounds__(256) void glens_kernel(const RtwSceneDev* __restrict__ sc, GroupBufs gb, RtwGroupParams g)
+{
+    const RtwRenderParams& p = g.rp;
+    const int npix = p.width * p.height;
+    Counters ct = { 0, 0, 0, 0, 0, 0 };
+    const uint32_t phase = table_phase(p.seed);
+    const uint32_t total = (uint32_t)g.n_jobs * (uint32_t)g.n_passes;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    const int lane = lane_id();
+    __shared__ uint32_t part[5];
+    uint32_t queued = 0u, tqueued = 0u, b = 0u, kpass = 0u, nsub = 1u, sub0 = 0u;
+    if (wave < total) {
+        const uint32_t jidx = wave / (uint32_t)g.n_passes;
+        kpass = wave - jidx * (uint32_t)g.n_passes;
+        const uint32_t job = g.jobs ? cldu(g.jobs, (int)jidx) : jidx;
+        b = job & 0xFFFFFFu;
+        const int only_sample = (int)((job >> 24) & 15u) - 1;        // -1: this wave does every sub-sample of its tile
+        nsub = only_sample >= 0 ? 1u : (uint32_t)p.sub_samples;
+        sub0 = only_sample >= 0 ? (uint32_t)only_sample : 0u;
+        const int wt = g.busy_tiles ? (int)cldu(g.busy_tiles, (int)b) : g.first_tile + (int)b;
+        int px = 0, py = 0;
+        const bool live = group_xy(g, wt, lane, px, py);
+        const int pixel = live ? py * p.width + px : 0;
+        const uint32_t pass = (uint32_t)g.first_pass + kpass;
+        for (uint32_t r = 0; r < nsub; r++) {
+            if (!live) continue;
+            const uint32_t i = nsub == 1u ? sub0 : r;
+            const uint32_t slot = group_slot(g, b, (uint32_t)lane, i, kpass);
+            if (p.max_bounce == 0) { gb.rad[slot] = make_float4(0.f, 0.f, 0.f, 0.f); continue; }      // RayTrace(.., 0) is black (Src/RayTracerScene.cpp:39)
+            PathRng rng; rng_init(rng, p.seed, phase, (uint64_t)npix, (uint32_t)pixel, pass, i);
+            const Ray ray = camera_ray_xy<true, true>(p, px, py, (int)i, rng, pass);
+            if (STATS) ct.cams++;
+            group_save_state(gb, slot, ray, rng, p.max_bounce, 0, pixel, (kpass << 2) | i);
+            queued |= 1u << r;
+            if (AN && p.lead_shapes > 0) {
+                float4 q0, q1;
+                if (group_lead_query<STATS>(sc, p.lead_shapes, ray, q0, q1, ct)) tqueued |= 1u << r;
+                GHT(gb, slot, 0) = q0; GHT(gb, slot, 1) = q1;
+            }
+        }
+    }
+    {
+        // list space reserved once per BLOCK (every wave of the block comes here, also one without a job), as in gprimary_kernel
+        const unsigned long long m0 = __ballot((queued & 1u) != 0u), m1 = __ballot((queued & 2u) != 0u), m2 = __ballot((queued & 4u) != 0u),
+                                 m3 = __ballot((queued & 8u) != 0u);
+        const uint32_t c0 = (uint32_t)__popcll(m0), c1 = (uint32_t)__popcll(m1), c2 = (uint32_t)__popcll(m2), c3 = (uint32_t)__popcll(m3);
+        const uint32_t qb = block_reserve<4>(&gb.counters[0], c0 + c1 + c2 + c3, part);
+        auto slot_of = [&](uint32_t r) { return group_slot(g, b, (uint32_t)lane, nsub == 1u ? sub0 : r, kpass); };
         if (queued & 1u) gb.list0[qb + (uint32_t)mbcnt(m0)] = slot_of(0u);
         if (queued & 2u) gb.list0[qb + c0 + (uint32_t)mbcnt(m1)] = slot_of(1u);
         if (queued & 4u) gb.list0[qb + c0 + c1 + (uint32_t)mbcnt(m2)] = slot_of(2u);

@@ -174,7 +174,13 @@ struct RtwRenderParams {
     const float* cam_dy;            // computed once on the host with the same float operations
     RtwCamera cam;                  // the scene's camera, by value (wave-uniform: scalar registers)
     int32_t cam_general;            // 0: cam is the default camera bit for bit -> the kernels' fixed-pose instantiations (constants instead of cam); 1: the general ones
+    // the thin lens (rtw_lens of rtwin.h), a launch parameter like the camera.  lens != 0 (aperture_radius > 0): every camera ray has its own origin on
+    // the aperture disc -> the kernels' LENS instantiations (which imply the general camera), no screen bins, every tile busy
+    int32_t lens;
+    float lens_radius, lens_focus;
 };
+// the lens point's random stream: stream_key(seed, pixel, (pass * 4 + sub) | RTW_LENS_STREAM), beside the path's own (whose counter the lens never moves)
+#define RTW_LENS_STREAM 0x80000000u
 
 // screen-space bins of one shape for one (width, height, tile shape): CSR over the bins, entries = node index of a leaf, ascending
 struct RtwBinsDev {

@@ -284,7 +284,7 @@ __global__ __launch_bounds__(256) void primary_sky_kernel(const float* __restric
 }
 
 // ---- primary rays through the screen bins ------------------------------------------------------------------------
-template <bool STATS, bool AN, bool CAM>
+template <bool STATS, bool AN, bool CAM, bool LENS = false>
 __global__ __launch_bounds__(256) void primary_bins_kernel(const RtwSceneDev* __restrict__ sc, float4* __restrict__ accum,
                                                            uint32_t* __restrict__ argb, PipeBufs pb, RtwRenderParams p)
 {
@@ -337,7 +337,7 @@ __global__ __launch_bounds__(256) void primary_bins_kernel(const RtwSceneDev* __
     for (int i = 0; i < p.sub_samples; i++) {                // wave-uniform loop
         if (only_sample >= 0 && i != only_sample) continue;
         PathRng rng; rng_init(rng, p.seed, phase, (uint64_t)npix, (uint32_t)(live ? pixel : 0), (uint32_t)p.pass_index, (uint32_t)i);
-        const Ray ray = camera_ray_xy<CAM>(p, px, py, i, rng);
+        const Ray ray = camera_ray_xy<CAM, LENS>(p, px, py, i, rng, (uint32_t)p.pass_index);
         if (STATS && live) ct.cams++;
         f3 si = mk(0, 0, 0);
         bool queue_it = false;

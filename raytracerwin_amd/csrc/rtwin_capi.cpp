@@ -149,6 +149,7 @@ struct rtw_context {
     // ray queries on device buffers (rtw_trace_closest_device / rtw_trace_occluded_device)
     int query_kernel = -1;              // option: 1 = qtrace_kernel, 0 = closest_kernel on the caller's buffers (the baseline and cross-check), -1 = the measured rule (query_uses_new_kernel)
     int query_blocks = 0;               // option: > 0 = at most exactly this many blocks
+    int lens_route = -1;                // option: pipeline 4 with a lens: 1 = the camera round (glens_kernel + the trace kernels), 0 = gprimary_kernel's LENS instantiation, -1 = the rule (lens_uses_camera_round)
     void* d_query_ws = nullptr;         // "query_kernel" 0 only: stand-ins for the outputs closest_kernel writes and the caller did not ask for (grown on demand)
     size_t query_ws_bytes = 0;
 };
@@ -179,6 +180,8 @@ struct rtw_scene {
     int prune = 1;
     int traversal = 1;
     RtwCamera camera = rtw_default_camera();    // rtw_scene_set_camera; travels by value in every launch's parameters
+    rtw_lens lens = { 0.0f, 1.0f };             // rtw_scene_set_lens; aperture_radius 0 = the pinhole.  A launch parameter too, not part of the device scene
+    bool has_lens() const { return lens.aperture_radius > 0.0f; }
     RtwSceneDev* d_scene = nullptr;
     std::vector<void*> allocs;
     size_t allocs_at_commit = 0;        // allocs past this mark are the screen bins and tile tables of the current camera
@@ -353,6 +356,7 @@ int rtw_context_set_option(rtw_context* ctx, const char* name, int value)
         return RTW_OK;
     }
     if (std::strcmp(name, "query_kernel") == 0) { ctx->query_kernel = value < 0 ? -1 : (value ? 1 : 0); return RTW_OK; }
+    if (std::strcmp(name, "lens_route") == 0) { ctx->lens_route = value < 0 ? -1 : (value ? 1 : 0); return RTW_OK; }
     if (std::strcmp(name, "query_blocks") == 0) { ctx->query_blocks = value < 0 ? 0 : value; return RTW_OK; }
     if (std::strcmp(name, "hint_period") == 0) { ctx->hint_period = value < 1 ? 1 : value; return RTW_OK; }
     if (std::strcmp(name, "kernel_timing") == 0) {
@@ -615,6 +619,26 @@ const char* camera_problem(const RtwCamera& c)
     }
     return nullptr;
 }
+const char* lens_problem(const rtw_lens& l)
+{
+    if (!std::isfinite(l.aperture_radius) || !std::isfinite(l.focus_distance)) return "lens: non-finite value";
+    if (l.aperture_radius < 0.0f) return "lens: aperture_radius must not be negative";
+    if (!(l.focus_distance > 0.0f)) return "lens: focus_distance must be positive";
+    return nullptr;
+}
+// camera and lens of a launch (by value in its parameters).  A lens implies the general camera; without one the lens fields stay zero.
+inline void set_camera_params(const rtw_scene* scene, RtwRenderParams& p)
+{
+    p.cam = scene->camera; p.cam_general = camera_is_default(scene->camera) ? 0 : 1;
+    p.lens = scene->has_lens() ? 1 : 0;
+    p.lens_radius = p.lens ? scene->lens.aperture_radius : 0.0f; p.lens_focus = p.lens ? scene->lens.focus_distance : 0.0f;
+    if (p.lens) p.cam_general = 1;
+}
+// "lens_route" -1: which route camera rays through a lens take in pipeline 4.  Measured in one session (profiles/lens_experiments.md): gprimary_kernel's LENS
+// instantiation won on all three scenes -- 0.088 against 0.351 ms per pass on TorusKnot 1080p (most rays miss the mesh's box, which the primary kernel finds
+// out before anything is stored, while the camera round writes and reads a slot for every path), 0.61 / 1.05 on unitychan, 0.79 / 0.81 on the
+// reference's default scene -- so the rule is that route; the camera round stays as the cross-check ("lens_route" 1).
+inline bool lens_uses_camera_round(const rtw_context* cx) { return cx->lens_route == 1; }
 // RMath::Random of the path's stream (rtw_device.hip PathRng::random)
 inline float camera_uniform(uint32_t seed, uint32_t pixel, uint32_t sample, uint32_t counter) { return (float)(int32_t)rtw::rand31(seed, pixel, sample, counter) / 2147483648.0f; }
 }  // namespace
@@ -668,13 +692,17 @@ int rtw_scene_get_camera(const rtw_scene* scene, rtw_camera* out)
     return RTW_OK;
 }
 
-int rtw_camera_rays(const rtw_camera* cam, int width, int height, const int32_t* pixels, int64_t n, int pass_index, int sub_sample, uint32_t seed, float* rays7)
+// rtw_camera_rays (lens null, or its aperture_radius 0: the pinhole ray, the code as it always was) and rtw_lens_rays
+static int camera_rays(const rtw_camera* cam, const rtw_lens* lens, int width, int height, const int32_t* pixels, int64_t n, int pass_index, int sub_sample, uint32_t seed, float* rays7)
 {
     if (width <= 0 || height <= 0 || n < 0 || (n > 0 && (!pixels || !rays7))) return fail(RTW_ERR_INVALID, "bad argument");
     if (pass_index < 0 || sub_sample < 0 || sub_sample > 3) return fail(RTW_ERR_INVALID, "pass_index >= 0 and sub_sample in 0..3");
     if ((int64_t)width * height > INT32_MAX) return fail(RTW_ERR_LIMIT, "frame too large");
     const RtwCamera c = cam ? to_internal(*cam) : rtw_default_camera();
     if (const char* why = camera_problem(c)) return fail(RTW_ERR_INVALID, why);
+    if (lens) { if (const char* why = lens_problem(*lens)) return fail(RTW_ERR_INVALID, why); }
+    const bool thin = lens && lens->aperture_radius > 0.0f;
+    if (thin && pass_index >= (1 << 29)) return fail(RTW_ERR_LIMIT, "pass_index must stay below 2^29 with a lens");
     const float aspect = (float)width / (float)height;
     const float inv_pixel_radius = 1.0f / (width * 4);
     const float offset_radius = inv_pixel_radius * 0.5f;
@@ -697,12 +725,65 @@ int rtw_camera_rays(const rtw_camera* cam, int width, int height, const int32_t*
             const float s = ra + ub;
             v[k] = s + ff;
         }
+        float* r = rays7 + (size_t)j * 7;
+        if (thin) {
+            // the lens point from its own stream (rtw_device.hip lens_point), then the ray of rtw_device.hip lens_ray_from
+            const uint32_t lsample = sample | RTW_LENS_STREAM;
+            float lx = 0.0f, ly = 0.0f;
+            for (uint32_t t = 0; t < 8u; t++) {
+                const float tx2 = 2.0f * camera_uniform(seed, (uint32_t)pixel, lsample, 2u * t), ty2 = 2.0f * camera_uniform(seed, (uint32_t)pixel, lsample, 2u * t + 1u);
+                const float tx = tx2 - 1.0f, ty = ty2 - 1.0f;
+                const float qx = tx * tx, qy = ty * ty; const float q = qx + qy;
+                if (q <= 1.0f) { lx = tx; ly = ty; break; }
+            }
+            const float s = lens->focus_distance / c.focal;
+            const float lxr = lx * lens->aperture_radius, lyr = ly * lens->aperture_radius;
+            float w[3];
+            for (int k = 0; k < 3; k++) {
+                const float rl = c.right[k] * lxr, ul = c.up[k] * lyr; const float off = rl + ul;
+                const float vs = v[k] * s;
+                r[k] = c.eye[k] + off; w[k] = vs - off;
+            }
+            const float xx = w[0] * w[0], yy = w[1] * w[1], zz = w[2] * w[2];
+            const float sq0 = xx + yy; const float sq = sq0 + zz;
+            const float inv = 1.0f / sqrtf(sq);
+            r[3] = w[0] * inv; r[4] = w[1] * inv; r[5] = w[2] * inv; r[6] = 1000.0f;
+            continue;
+        }
         const float xx = v[0] * v[0], yy = v[1] * v[1], zz = v[2] * v[2];
         const float sq0 = xx + yy; const float sq = sq0 + zz;
         if (!(std::fabs(sq) < FLT_EPSILON)) { const float inv = 1.0f / sqrtf(sq); v[0] *= inv; v[1] *= inv; v[2] *= inv; }
-        float* r = rays7 + (size_t)j * 7;
         r[0] = c.eye[0]; r[1] = c.eye[1]; r[2] = c.eye[2]; r[3] = v[0]; r[4] = v[1]; r[5] = v[2]; r[6] = 1000.0f;
     }
+    return RTW_OK;
+}
+
+int rtw_camera_rays(const rtw_camera* cam, int width, int height, const int32_t* pixels, int64_t n, int pass_index, int sub_sample, uint32_t seed, float* rays7)
+{
+    return camera_rays(cam, nullptr, width, height, pixels, n, pass_index, sub_sample, seed, rays7);
+}
+
+int rtw_lens_rays(const rtw_camera* cam, const rtw_lens* lens, int width, int height, const int32_t* pixels, int64_t n, int pass_index, int sub_sample, uint32_t seed, float* rays7)
+{
+    return camera_rays(cam, lens, width, height, pixels, n, pass_index, sub_sample, seed, rays7);
+}
+
+int rtw_scene_set_lens(rtw_scene* scene, const rtw_lens* lens)
+{
+    if (!scene) return fail(RTW_ERR_INVALID, "scene is null");
+    const rtw_lens l = lens ? *lens : rtw_lens{ 0.0f, 1.0f };
+    if (const char* why = lens_problem(l)) return fail(RTW_ERR_INVALID, why);
+    if (std::memcmp(&l, &scene->lens, sizeof l) == 0) return RTW_OK;
+    // with a lens no mesh has bins and every tile is busy: the cached bins and tile tables belong to the other kind of frame
+    if (scene->committed && scene->ctx) { const int rc = drop_camera_tables(scene); if (rc != RTW_OK) return rc; }
+    scene->lens = l;
+    return RTW_OK;
+}
+
+int rtw_scene_get_lens(const rtw_scene* scene, rtw_lens* out)
+{
+    if (!scene || !out) return fail(RTW_ERR_INVALID, "null argument");
+    *out = scene->lens;
     return RTW_OK;
 }
 
@@ -914,6 +995,7 @@ int rtw_scene_mesh_bins(const rtw_scene* scene, int shape, int width, int height
     if (!counts2) return fail(RTW_ERR_INVALID, "null argument");
     std::vector<uint32_t> off, ent;
     bool ok;
+    if (scene->has_lens()) { counts2[0] = 0; counts2[1] = 0; return 0; }       // rays that start all over the aperture: no mesh gets bins (scene_bins)
     if (scene->ctx && scene->ctx->device_build && scene->d_nodes_of.size() > (size_t)shape && scene->d_nodes_of[(size_t)shape]) {
         // what the renderer uses: the lists built on the device
         if (width <= 0 || height <= 0 || bin_w <= 0 || bin_h <= 0) return fail(RTW_ERR_INVALID, "bad bin geometry");
@@ -1229,6 +1311,8 @@ static int scene_bins(rtw_scene* scene, int width, int height, int bin_w, int bi
         std::vector<uint32_t> off, ent;
         h[s].off = nullptr; h[s].ent = nullptr;
         if (scene->meshes[s]->kind != RTW_SHAPE_MESH) { for (auto& w : weight) w += 1u; continue; }      // tested by every sample of every tile
+        // a lens: the projection from `eye` no longer bounds what a tile's rays can meet -> no bins, every tile of a scene with a mesh is busy
+        if (scene->has_lens()) { for (auto& w : weight) w += 1000u; continue; }
         if (scene->ctx->device_build && scene->d_nodes_of.size() > s && scene->d_nodes_of[s]) {
             // the same lists from the device: counted, scanned, filled and sorted there (rtw_build_kernels.h); only the offsets come back (tile weights)
             off.resize(n_bins + 1);
@@ -1447,6 +1531,7 @@ static int check_render_args(const rtw_scene* scene, const rtw_framebuffer* fb, 
     if (max_bounce < 0 || max_bounce > RTW_MAX_BOUNCE) return fail(RTW_ERR_LIMIT, "max_bounce out of range");
     if (sub_samples < 1 || sub_samples > 4) return fail(RTW_ERR_INVALID, "sub_samples must be 1..4");
     if (pass_index < 0) return fail(RTW_ERR_INVALID, "pass_index must be >= 0");
+    if (scene->has_lens() && pass_index >= (1 << 29)) return fail(RTW_ERR_LIMIT, "pass_index must stay below 2^29 with a lens");      // (the lens stream's key: pass * 4 + sub with bit 31 set)
     return RTW_OK;
 }
 
@@ -1576,7 +1661,7 @@ static int render_group(rtw_scene* scene, rtw_framebuffer* fb, const GroupReques
     bool ranged = q.ranged;
     p.width = fb->width; p.height = fb->height;
     p.max_bounce = max_bounce; p.preview = q.use_base_color ? 1 : 0; p.pass_index = first_pass; p.sub_samples = sub_samples; p.seed = q.seed;
-    p.cam = scene->camera; p.cam_general = camera_is_default(scene->camera) ? 0 : 1;
+    set_camera_params(scene, p);
     if (!choose_group_tiles(p, range_begin, range_end)) return fail(RTW_ERR_LIMIT, "frame too large for the tile mapping");
     rtw_scene::BinSet* bs = nullptr;
     int rc = scene_bins(scene, p.width, p.height, p.tile_w, p.tile_h, &bs); if (rc != RTW_OK) return rc;
@@ -1643,6 +1728,8 @@ static int render_group(rtw_scene* scene, rtw_framebuffer* fb, const GroupReques
     // (keyed by the launch shape WITHOUT the number of passes: the lengths are kept per pass and scaled to the group at hand, so a warm-up call of any
     // length primes a longer one)
     rtw_context::GroupKey key; key.scene = scene; key.capacity = (long long)((size_t)g.n_busy * 64 * (size_t)sub_samples); key.max_bounce = max_bounce; key.preview = p.preview; key.n_passes = 0;
+    const bool camera_round = p.lens != 0 && lens_uses_camera_round(cx);
+    if (camera_round) key.n_passes = -2;       // (its lists are one round later: the lengths of the other kind of group say nothing)
     if (cx->gcounters_pending && hipEventQuery(cx->gcounters_event) == hipSuccess) {
         cx->known_gkey = cx->gcounters_key; cx->gcounters_pending = false;
         const int np = cx->gcounters_passes > 0 ? cx->gcounters_passes : 1;
@@ -1656,6 +1743,7 @@ static int render_group(rtw_scene* scene, rtw_framebuffer* fb, const GroupReques
     for (int r = 0; r < 16; r++) tune.overflow_hint[r] = (cx->known_gkey == key) ? scaled(cx->known_goverflow[r]) : -1;
     for (int r = 0; r < 16; r++) tune.trace_hint[r] = (cx->known_gkey == key) ? scaled(cx->known_gtrace[r]) : -1;
     tune.skip_trace = facts.all_lead;
+    tune.camera_round = camera_round;
     bool& clean = cx->group_clean[q.part];
     const bool sky_only = tune.sky_mode == 2;       // (touches neither the workspace nor its counters)
     if (!sky_only) clean = false;
@@ -1684,7 +1772,7 @@ static int render_common(rtw_scene* scene, rtw_framebuffer* fb, RtwRenderParams&
     int rc = check_render_args(scene, fb, max_bounce, pass_index, sub_samples); if (rc != RTW_OK) return rc;
     p.width = fb->width; p.height = fb->height;
     p.max_bounce = max_bounce; p.preview = use_base_color ? 1 : 0; p.pass_index = pass_index; p.sub_samples = sub_samples; p.seed = seed;
-    p.cam = scene->camera; p.cam_general = camera_is_default(scene->camera) ? 0 : 1;
+    set_camera_params(scene, p);
     rtw_context* cx = scene->ctx;
     hipError_t e;
     // the bins + wave pipeline needs whole rows, the flat hierarchy (traversal != 0) and a frame that tiles; a scene whose analytic hits can inherit a texel
@@ -1806,6 +1894,7 @@ int rtw_render_passes(rtw_scene* scene, rtw_framebuffer* fb, int task_rows, int 
     int rc = need_committed(scene); if (rc != RTW_OK) return rc;
     if (!fb) return fail(RTW_ERR_INVALID, "framebuffer is null");
     if (n_passes < 0 || first_pass < 0) return fail(RTW_ERR_INVALID, "bad pass range");
+    if (scene->has_lens() && (long long)first_pass + n_passes > (1ll << 29)) return fail(RTW_ERR_LIMIT, "pass_index must stay below 2^29 with a lens");
     rtw_context* cx = scene->ctx;
     if (!group_pipeline_ok(scene)) {
         // pipelines 3 / 0: a pass per set of launches; the passes of this call form a run (the second stream is forked before the first and joined after the last)

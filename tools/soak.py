@@ -5,7 +5,7 @@
 
 Every case draws a scene (one of the three OBJ assets, two of them together, random spheres / planes / capsules alone or around a
 mesh, or a random triangle soup with degenerate, axis-aligned, coincident and behind-the-camera triangles), a material tree, a frame shape (including tall / narrow / odd sizes),
-spp, depth, preview flag, passes, a rank split and random pipeline options, renders it through the one-thread-per-pixel kernel
+spp, depth, preview flag, passes, a rank split, in a quarter of the cases a thin lens, and random pipeline options, renders it through the one-thread-per-pixel kernel
 (pipeline 0, the most literal reading of ThreadWorker_Render, Src/RayTracerProgram.cpp:130-189) and through the default bins + wave
 pipeline, and compares accumulator and ARGB bits.  Prints one line per case and the number of mismatches; exit code 1 on any."""
 import argparse
@@ -70,7 +70,7 @@ def material(rng, depth=0):
     return R.SurfaceMaterial_Null()
 
 
-DEFAULTS = dict(pipeline=4, group_max=256, wave_below=80000, visit_budget=384, group_split=1, split_min=8, split_paths=400000, workspace_limit_mb=0, primary_passes=0)
+DEFAULTS = dict(pipeline=4, group_max=256, wave_below=80000, visit_budget=384, group_split=1, split_min=8, split_paths=400000, workspace_limit_mb=0, primary_passes=0, lens_route=-1)
 
 
 def run(seed_arg, cases, ctx=None, log=print, only=-1, pipelines=(0, 3, 4), keep=None, override=None):
@@ -109,6 +109,10 @@ def run(seed_arg, cases, ctx=None, log=print, only=-1, pipelines=(0, 3, 4), keep
                      group_split=int(rng.random() < 0.8), split_min=int(rng.choice([2, 2, 4, 8])), split_paths=int(rng.choice([0, 0, 400000])),
                      workspace_limit_mb=int(rng.choice([0, 0, 0, 1, 8])),
                      primary_passes=[0, -1, 2, 4][(seed >> 3) & 3])       # (from the case's seed: no extra draw, so the cases of a soak seed stay what they were)
+        # a thin lens in a quarter of the cases, through either route of pipeline 4 (from the case's seed too: no extra draw)
+        lens = R.Lens([0.05, 0.3][(seed >> 7) & 1], [2.0, 7.0][(seed >> 8) & 1]) if (seed >> 5) & 3 == 0 else None
+        gopts["lens_route"] = (seed >> 9) & 1 if lens is not None else -1
+        s.set_lens(lens)
         if override:
             gopts.update(override)
         if only >= 0 and it != only:        # replay of one case: the others only advance the generator
