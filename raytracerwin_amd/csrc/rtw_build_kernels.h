@@ -247,9 +247,7 @@ __global__ __launch_bounds__(256) void build_level_kernel(const float* __restric
     }
 }
 
-// leaf records in leaf order: the triangle with the face normal RRay::TestIntersectionWithTriangle recomputes at every test
-// (Src/RRay.cpp:138-145: normalize(cross(p1 - p0, p2 - p0)), tiny vectors left as they are) and the shading inputs
-// RMeshShape::TestRayIntersection gathers per hit (Src/MeshShape.cpp:303-326)
+// leaf records in leaf order (rtw_shared.h tri_record, shade_record)
 __global__ void build_leaf_records_kernel(const float* __restrict__ pts, const float* __restrict__ tcs, const float* __restrict__ nrm,
                                           const int32_t* __restrict__ idx_p, const int32_t* __restrict__ idx_t, const int32_t* __restrict__ idx_n,
                                           const int32_t* __restrict__ mat, const int32_t* __restrict__ leaf_order, int n_tris, RtwTri* __restrict__ tris, RtwShade* __restrict__ shade)
@@ -259,21 +257,10 @@ __global__ void build_leaf_records_kernel(const float* __restrict__ pts, const f
     const int t = leaf_order[s];
     const int a = idx_p[t * 3], b = idx_p[t * 3 + 1], c = idx_p[t * 3 + 2];
     const f3 p0 = mk(pts[a * 3], pts[a * 3 + 1], pts[a * 3 + 2]), p1 = mk(pts[b * 3], pts[b * 3 + 1], pts[b * 3 + 2]), p2 = mk(pts[c * 3], pts[c * 3 + 1], pts[c * 3 + 2]);
-    const f3 n = normalized(cross(p1 - p0, p2 - p0));
-    RtwTri r;
-    r.p0x = p0.x; r.p0y = p0.y; r.p0z = p0.z; r.nx = n.x;
-    r.p1x = p1.x; r.p1y = p1.y; r.p1z = p1.z; r.ny = n.y;
-    r.p2x = p2.x; r.p2y = p2.y; r.p2z = p2.z; r.nz = n.z;
-    r.d1 = dot(n, p0); r.orig = t; r.pad0 = r.pad1 = 0;
-    tris[s] = r;
-    RtwShade sh;
+    tris[s] = tri_record(p0, p1, p2, t);
     const int na = idx_n[t * 3], nb = idx_n[t * 3 + 1], nc = idx_n[t * 3 + 2], ta = idx_t[t * 3], tb = idx_t[t * 3 + 1], tc = idx_t[t * 3 + 2];
-    sh.n0x = nrm[na * 3]; sh.n0y = nrm[na * 3 + 1]; sh.n0z = nrm[na * 3 + 2];
-    sh.n1x = nrm[nb * 3]; sh.n1y = nrm[nb * 3 + 1]; sh.n1z = nrm[nb * 3 + 2];
-    sh.n2x = nrm[nc * 3]; sh.n2y = nrm[nc * 3 + 1]; sh.n2z = nrm[nc * 3 + 2];
-    sh.u0 = tcs[ta * 3]; sh.v0 = tcs[ta * 3 + 1]; sh.u1 = tcs[tb * 3]; sh.v1 = tcs[tb * 3 + 1]; sh.u2 = tcs[tc * 3]; sh.v2 = tcs[tc * 3 + 1];
-    sh.material = mat[t];
-    shade[s] = sh;
+    shade[s] = shade_record(mk(nrm[na * 3], nrm[na * 3 + 1], nrm[na * 3 + 2]), mk(nrm[nb * 3], nrm[nb * 3 + 1], nrm[nb * 3 + 2]), mk(nrm[nc * 3], nrm[nc * 3 + 1], nrm[nc * 3 + 2]),
+                            mk(tcs[ta * 3], tcs[ta * 3 + 1], 0.0f), mk(tcs[tb * 3], tcs[tb * 3 + 1], 0.0f), mk(tcs[tc * 3], tcs[tc * 3 + 1], 0.0f), mat[t]);
 }
 
 // place[i] of every node in the explicit-link array: the nodes of depth <= D first (preorder), the deeper ones after them (preorder);
@@ -313,106 +300,29 @@ __global__ void build_tnodes_kernel(const RtwNode* __restrict__ nodes, const int
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_nodes) return;
-    const RtwNode s = nodes[i];
-    RtwPNode t;
-    t.min_x = s.min_x; t.max_x = s.max_x; t.min_y = s.min_y; t.max_y = s.max_y; t.min_z = s.min_z; t.max_z = s.max_z;
-    t.skip = place[s.skip];
-    t.link = s.tri >= 0 ? s.tri : -1 - place[i + 1];
-    tnodes[place[i]] = t;
+    tnodes[place[i]] = link_record(nodes[i], place, i);
 }
 
-// flat hierarchy: level 0 = the leaves' own boxes by slot; level l + 1 entry k = union of level l entries [16 k, 16 k + 16)
+// flat hierarchy: level 0 = the leaves' own boxes by slot, then the unions (rtw_shared.h flat_leaf_entry, flat_union_entry)
 __global__ void build_flat0_kernel(const RtwNode* __restrict__ nodes, int n_nodes, float* __restrict__ flat0)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_nodes) return;
     const RtwNode s = nodes[i];
     if (s.tri < 0) return;
-    float* e = flat0 + (size_t)s.tri * 6;
-    e[0] = s.min_x; e[1] = s.max_x; e[2] = s.min_y; e[3] = s.max_y; e[4] = s.min_z; e[5] = s.max_z;
+    flat_leaf_entry(s, flat0 + (size_t)s.tri * 6);
 }
 __global__ void build_flat_up_kernel(const float* __restrict__ lower, int n_lower, float* __restrict__ upper, int n_upper)
 {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n_upper) return;
-    float lo[3] = { FLT_MAX, FLT_MAX, FLT_MAX }, hi[3] = { -FLT_MAX, -FLT_MAX, -FLT_MAX };
-    for (int i = 16 * k; i < 16 * k + 16 && i < n_lower; i++)
-        for (int c = 0; c < 3; c++) {
-            const float a = lower[(size_t)i * 6 + 2 * c], b = lower[(size_t)i * 6 + 2 * c + 1];
-            if (a < lo[c]) lo[c] = a;
-            if (b > hi[c]) hi[c] = b;
-        }
-    for (int c = 0; c < 3; c++) { upper[(size_t)k * 6 + 2 * c] = lo[c]; upper[(size_t)k * 6 + 2 * c + 1] = hi[c]; }
+    flat_union_entry(lower, n_lower, upper, k);
 }
 
 // ---- screen-space bins of the scene's camera (rtw_types.h RtwBinsCam), built on the device ------------------------------------------
-// The host routine (scene_host.cpp build_bins) operation for operation, in double precision: a leaf is listed in the bins its triangle's
-// projection (grown by the jitter margin) touches when the triangle faces the camera by the reference's own float test.  Three passes:
-// count per bin, scan, fill (any order), then every bin's list sorted ascending = preorder.
-struct BinsGeom { int width, height, bin_w, bin_h, bx, by; double margin; RtwBinsCam cam; };     // margin = cam.margin (rtw_types.h rtw_bins_camera)
-
-// the bins of one leaf: calls f(bin) for every bin the leaf is listed in; returns false when the MESH gets no bins at all
-template <typename F>
-__device__ __forceinline__ bool bins_of_leaf(const RtwNode& nd, const RtwTri& t, const BinsGeom& g, F f)
-{
-    const double cx = (double)(g.width / 2), cy = (double)(g.height / 2);
-    const RtwBinsCam& cam = g.cam;
-    for (int c = 0; c < 8; c++) {                           // a corner not in front of the eye: no bins for this mesh
-        const double qx = (double)((c & 1) ? nd.max_x : nd.min_x) - cam.eye[0], qy = (double)((c & 2) ? nd.max_y : nd.min_y) - cam.eye[1],
-                     qz = (double)((c & 4) ? nd.max_z : nd.min_z) - cam.eye[2];
-        const double depth = qx * cam.forward[0] + qy * cam.forward[1] + qz * cam.forward[2];
-        if (!(depth > 0.01)) return false;
-    }
-    {
-        const float ox = cam.eye_f[0], oy = cam.eye_f[1], oz = cam.eye_f[2];
-        const float d0 = t.nx * ox + t.ny * oy + t.nz * oz;
-        const float d2 = d0 - t.d1;
-        if (d2 < 0) return true;                            // faces away from every camera ray: listed nowhere
-    }
-    const double vx[3] = { t.p0x, t.p1x, t.p2x }, vy[3] = { t.p0y, t.p1y, t.p2y }, vz[3] = { t.p0z, t.p1z, t.p2z };
-    double sx[3], sy[3];
-    bool finite = true;
-    for (int k = 0; k < 3; k++) {
-        const double qx = vx[k] - cam.eye[0], qy = vy[k] - cam.eye[1], qz = vz[k] - cam.eye[2];
-        const double depth = qx * cam.forward[0] + qy * cam.forward[1] + qz * cam.forward[2];
-        const double qr = qx * cam.right[0] + qy * cam.right[1] + qz * cam.right[2], qu = qx * cam.up[0] + qy * cam.up[1] + qz * cam.up[2];
-        sx[k] = cx - cam.k * qr / depth; sy[k] = cy - cam.k * qu / depth;
-        finite = finite && sx[k] == sx[k] && sy[k] == sy[k] && fabs(sx[k]) < 1e12 && fabs(sy[k]) < 1e12;
-    }
-    if (!finite) return false;
-    const double xa = fmin(sx[0], fmin(sx[1], sx[2])), xb = fmax(sx[0], fmax(sx[1], sx[2]));
-    const double ya = fmin(sy[0], fmin(sy[1], sy[2])), yb = fmax(sy[0], fmax(sy[1], sy[2]));
-    double fx0 = floor(xa - g.margin), fx1 = ceil(xb + g.margin), fy0 = floor(ya - g.margin), fy1 = ceil(yb + g.margin);
-    if (fx1 < 0 || fy1 < 0 || fx0 > g.width - 1 || fy0 > g.height - 1) return true;      // off screen
-    if (fx0 < 0) fx0 = 0;
-    if (fy0 < 0) fy0 = 0;
-    if (fx1 > g.width - 1) fx1 = g.width - 1;
-    if (fy1 > g.height - 1) fy1 = g.height - 1;
-    const int bx0 = (int)fx0 / g.bin_w, bx1 = (int)fx1 / g.bin_w, by0 = (int)fy0 / g.bin_h, by1 = (int)fy1 / g.bin_h;
-    const double area2 = (sx[1] - sx[0]) * (sy[2] - sy[0]) - (sx[2] - sx[0]) * (sy[1] - sy[0]);
-    const double scale = fabs(xb - xa) + fabs(yb - ya) + 1.0;
-    const bool use_edges = fabs(area2) > 1e-9 * scale * scale;
-    for (int yb_ = by0; yb_ <= by1; yb_++) {
-        for (int xb_ = bx0; xb_ <= bx1; xb_++) {
-            bool separated = false;
-            if (use_edges) {
-                const double rx0 = (double)(xb_ * g.bin_w) - g.margin, rx1 = (double)(xb_ * g.bin_w + g.bin_w - 1) + g.margin;
-                const double ry0 = (double)(yb_ * g.bin_h) - g.margin, ry1 = (double)(yb_ * g.bin_h + g.bin_h - 1) + g.margin;
-                for (int e = 0; e < 3 && !separated; e++) {
-                    const int a = e, b2 = (e + 1) % 3, c = (e + 2) % 3;
-                    double nx = sy[b2] - sy[a], ny = -(sx[b2] - sx[a]);
-                    if (nx * (sx[c] - sx[a]) + ny * (sy[c] - sy[a]) > 0) { nx = -nx; ny = -ny; }
-                    const double len = sqrt(nx * nx + ny * ny);
-                    if (!(len > 0)) continue;
-                    const double px = nx > 0 ? rx0 : rx1, py = ny > 0 ? ry0 : ry1;
-                    if ((nx * (px - sx[a]) + ny * (py - sy[a])) / len > 1e-6) separated = true;
-                }
-            }
-            if (!separated) f(yb_ * g.bx + xb_);
-        }
-    }
-    return true;
-}
+// rtw_shared.h bins_of_leaf, the routine the host's build_bins calls, with a lane per leaf.  Three passes: count per bin, scan, fill (any
+// order), then every bin's list sorted ascending = preorder.
+struct BinsGeom : RtwBinsGeom {};       // the kernels' parameter type
 
 // pass 0: counts[bin] += 1 per listed leaf; pass 1: entries at off[bin] + (a ticket from fill[bin])
 template <int PASS>

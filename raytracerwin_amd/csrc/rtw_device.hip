@@ -17,6 +17,7 @@
 #include <type_traits>
 
 #include "rtw_types.h"
+#include "rtw_shared.h"
 #include "rtw_device.h"
 
 #ifdef RTW_TIMING
@@ -25,27 +26,15 @@ __device__ unsigned long long g_rtw_timing[12 * 16384];
 
 namespace {
 
-struct f3 { float x, y, z; };
-__device__ __forceinline__ f3 mk(float x, float y, float z) { f3 r; r.x = x; r.y = y; r.z = z; return r; }
-__device__ __forceinline__ f3 operator+(f3 a, f3 b) { return mk(a.x + b.x, a.y + b.y, a.z + b.z); }
-__device__ __forceinline__ f3 operator-(f3 a, f3 b) { return mk(a.x - b.x, a.y - b.y, a.z - b.z); }
+// f3, mk, + and -, dot, cross, near_zero, normalized: rtw_shared.h
 __device__ __forceinline__ f3 operator*(f3 a, float s) { return mk(a.x * s, a.y * s, a.z * s); }
 __device__ __forceinline__ f3 operator*(f3 a, f3 b) { return mk(a.x * b.x, a.y * b.y, a.z * b.z); }
 __device__ __forceinline__ f3 operator/(f3 a, float s) { return mk(a.x / s, a.y / s, a.z / s); }
-__device__ __forceinline__ float dot(f3 a, f3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ f3 cross(f3 a, f3 b) { return mk(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
-__device__ __forceinline__ bool near_zero(float a) { return fabsf(a) < FLT_EPSILON; }   // FLT_EQUAL_ZERO
 __device__ __forceinline__ f3 reflect(f3 v, f3 n) { return v - (n * 2.0f) * dot(v, n); } // Src/RVector.h:218
 __device__ __forceinline__ bool all_nonzero(f3 a) { return !near_zero(a.x) && !near_zero(a.y) && !near_zero(a.z); } // :142
 __device__ __forceinline__ float ref_min(float a, float b) { return (a < b) ? a : b; }  // Math::Min
 __device__ __forceinline__ float ref_max(float a, float b) { return (a > b) ? a : b; }  // Math::Max
 
-__device__ __forceinline__ f3 normalized(f3 v)          // RVec3::GetNormalizedVec3
-{
-    float sq = v.x * v.x + v.y * v.y + v.z * v.z;
-    if (!near_zero(sq)) { float inv = 1.0f / sqrtf(sq); v.x *= inv; v.y *= inv; v.z *= inv; }
-    return v;
-}
 __device__ __forceinline__ float q_rsqrt(float number)  // Math::Q_rsqrt (Src/MathHelper.cpp:26-38)
 {
     const float x2 = number * 0.5f;
@@ -60,14 +49,7 @@ __device__ __forceinline__ f3 normalized_fast(f3 v)     // RVec3::GetNormalizedV
     return v;
 }
 
-// ---- random stream (specification shared with the oracle) --------------------------------
-__device__ __forceinline__ uint32_t mix32(uint32_t x) { x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16; return x; }
-__device__ __forceinline__ uint32_t stream_key(uint32_t seed, uint32_t pixel, uint32_t sample)
-{
-    uint32_t h = mix32(seed ^ 0x9E3779B9u);
-    h = mix32(h + pixel);
-    return mix32(h + sample);
-}
+// ---- a path's state of the random stream (rtw_shared.h) --------------------------------
 struct PathRng {
     uint32_t key, counter;
     uint64_t table_base;    // first unit-table index of the path, phase included, before the modulo
@@ -75,13 +57,8 @@ struct PathRng {
     // the unit-table entry the NEXT hemisphere draw will read, fetched ahead of the shading chain (valid while
     // pre_reads == table_reads); a latency optimisation only: the value is the one the draw would load
     uint32_t pre_reads; float pre_x, pre_y, pre_z;
-    __device__ __forceinline__ float random()            // RMath::Random (Src/Math.h:17-20)
-    {
-        uint32_t r = mix32(key + counter++) >> 1;
-        return (float)(int32_t)r / 2147483648.0f;
-    }
+    __device__ __forceinline__ float random() { return stream_uniform(key, counter++); }
 };
-__device__ __forceinline__ uint32_t table_phase(uint32_t seed) { return mix32(seed ^ 0x7AB1E5u) % RTW_TABLE_SIZE; }   // 32-bit: fine
 __device__ __forceinline__ void rng_init(PathRng& r, uint32_t seed, uint32_t phase, uint64_t npix, uint32_t pixel, uint32_t pass, uint32_t sub)
 {
     r.key = stream_key(seed, pixel, pass * 4u + sub);
@@ -765,92 +742,57 @@ __device__ f3 trace_path(const RtwSceneDev* __restrict__ sc, const TravCtx& tc, 
 
 // ---- camera + resolve (Src/RayTracerProgram.cpp:131-188, Src/ColorBuffer.h:81-109) ---------------------------
 // CAM = false: the reference's fixed camera as constants (the code every default-pose frame has always run);
-// CAM = true: the scene's camera from the launch parameters (rtw_types.h RtwCamera: every product and every sum rounded on its own)
-template <bool CAM>
-__device__ __forceinline__ f3 camera_view(const RtwCamera& c, float a, float b)        // v of rtw_types.h RtwCamera, before it is normalised
-{
-    if (CAM) return mk((c.right[0] * a + c.up[0] * b) + c.forward[0] * c.focal,
-                       (c.right[1] * a + c.up[1] * b) + c.forward[1] * c.focal,
-                       (c.right[2] * a + c.up[2] * b) + c.forward[2] * c.focal);
-    return mk(a, b, -0.5f);
-}
+// CAM = true: the scene's camera from the launch parameters (rtw_shared.h camera_view)
 template <bool CAM>
 __device__ __forceinline__ f3 camera_eye(const RtwCamera& c) { return CAM ? mk(c.eye[0], c.eye[1], c.eye[2]) : mk(0, 0, 7.0f); }
-template <bool CAM>
-__device__ __forceinline__ Ray camera_ray_from(const RtwCamera& c, float a, float b)
+// where sub-sample i of a pixel looks through, (a, b) = (dx + ox, dy + oy): the offset and the jitter (the path's first two draws) on the
+// pixel's dx and dy -- the one body of camera_ray and camera_ray_xy, which differ in where dx and dy come from
+__device__ __forceinline__ void sample_through(const RtwRenderParams& p, float dx, float dy, int i, PathRng& rng, float& a, float& b)
+{
+    float ox, oy, offset_radius;
+    sample_grid(p.width, i, ox, oy, offset_radius);
+    ox = jittered(ox, rng.random(), offset_radius);
+    oy = jittered(oy, rng.random(), offset_radius);
+    a = dx + ox; b = dy + oy;
+}
+// The ray through (a, b): the pinhole's from the eye, or with a thin lens (rtw_shared.h lens_point, lens_ray) from a lens point out of the stream
+// stream_key(seed, pixel, (pass * 4 + i) | RTW_LENS_STREAM) -- `pixel`, `pass`: the sample's pixel and pass, unused without a lens
+template <bool CAM, bool LENS>
+__device__ __forceinline__ Ray ray_through(const RtwRenderParams& p, float a, float b, uint32_t pixel, int i, uint32_t pass)
 {
     Ray r;
-    r.o = camera_eye<CAM>(c);
-    r.d = normalized(camera_view<CAM>(c, a, b));
-    r.dist = 1000.0f;
-    return r;
-}
-
-// ---- the thin lens (rtw_lens of rtwin.h) ----
-// The point on the unit disc: rejection sampling, at most eight tries, from a stream of its own -- key_l = stream_key(seed, pixel,
-// (pass * 4 + sub) | RTW_LENS_STREAM), try t reads counters 2 t and 2 t + 1 -- so the path's own stream stands at counter 2 after the camera
-// ray with or without a lens.  No try inside the disc (4.5e-6 of the samples): the centre.
-__device__ __forceinline__ float lens_uniform(uint32_t key_l, uint32_t c) { return (float)(int32_t)(mix32(key_l + c) >> 1) / 2147483648.0f; }
-__device__ __forceinline__ void lens_point(uint32_t key_l, float& lx, float& ly)
-{
-    lx = 0.0f; ly = 0.0f;
-    for (uint32_t t = 0; t < 8u; t++) {
-        const float x = 2.0f * lens_uniform(key_l, 2u * t) - 1.0f, y = 2.0f * lens_uniform(key_l, 2u * t + 1u) - 1.0f;
-        if (x * x + y * y <= 1.0f) { lx = x; ly = y; break; }
+    if (LENS) {
+        const uint32_t key_l = stream_key(p.seed, pixel, (pass * 4u + (uint32_t)i) | RTW_LENS_STREAM);
+        const f3 v = camera_view(p.cam, a, b);
+        float lx, ly;
+        lens_point(key_l, lx, ly);
+        lens_ray(p.cam, p.lens_radius, p.lens_focus, v, lx, ly, r.o, r.d);
+    } else {
+        r.o = camera_eye<CAM>(p.cam);
+        r.d = normalized(CAM ? camera_view(p.cam, a, b) : mk(a, b, -0.5f));
     }
-}
-// The ray through the point focus_distance along `forward` that the pinhole ray of (a, b) meets, from the lens point: every product and every
-// sum rounded on its own (include/rtwin.h spells the steps out; rtw_lens_rays and the tests' NumPy model repeat them).
-__device__ __forceinline__ Ray lens_ray_from(const RtwRenderParams& p, float a, float b, uint32_t key_l)
-{
-    const RtwCamera& c = p.cam;
-    const f3 v = camera_view<true>(c, a, b);
-    float lx, ly;
-    lens_point(key_l, lx, ly);
-    const float s = p.lens_focus / c.focal;
-    const float lxr = lx * p.lens_radius, lyr = ly * p.lens_radius;
-    const f3 off = mk(c.right[0] * lxr + c.up[0] * lyr, c.right[1] * lxr + c.up[1] * lyr, c.right[2] * lxr + c.up[2] * lyr);
-    const f3 w = mk(v.x * s - off.x, v.y * s - off.y, v.z * s - off.z);
-    const float inv = 1.0f / sqrtf((w.x * w.x + w.y * w.y) + w.z * w.z);
-    Ray r;
-    r.o = mk(c.eye[0] + off.x, c.eye[1] + off.y, c.eye[2] + off.z);
-    r.d = mk(w.x * inv, w.y * inv, w.z * inv);
     r.dist = 1000.0f;
     return r;
 }
-
-// `pass`: the pass the sample belongs to (the lens stream's key needs it; unused without a lens)
 template <bool CAM, bool LENS = false>
 __device__ __forceinline__ Ray camera_ray(const RtwRenderParams& p, int pixel, int i, PathRng& rng, uint32_t pass = 0u)
 {
     const int width = p.width, height = p.height;
-    const float aspect = (float)width / (float)height;
+    const float aspect = frame_aspect(width, height);
     const int x = pixel % width, y = pixel / width;
-    const float dx = -(float)(x - width / 2) / (width * 2) * aspect;
-    const float dy = -(float)(y - height / 2) / (height * 2);
-    const float inv_pixel_radius = 1.0f / (width * 4);
-    const float offset_radius = inv_pixel_radius * 0.5f;
-    float ox = (i & 1) ? inv_pixel_radius : 0.0f;
-    float oy = (i & 2) ? inv_pixel_radius : 0.0f;
-    ox += (rng.random() - 0.5f) * offset_radius;
-    oy += (rng.random() - 0.5f) * offset_radius;
-    if (LENS) return lens_ray_from(p, dx + ox, dy + oy, stream_key(p.seed, (uint32_t)pixel, (pass * 4u + (uint32_t)i) | RTW_LENS_STREAM));
-    return camera_ray_from<CAM>(p.cam, dx + ox, dy + oy);
+    const float dx = pixel_dx(x, width, aspect);
+    const float dy = pixel_dy(y, height);
+    float a, b;
+    sample_through(p, dx, dy, i, rng, a, b);
+    return ray_through<CAM, LENS>(p, a, b, (uint32_t)pixel, i, pass);
 }
-
-// the same ray from the host's per-column / per-row tables (tiled pipelines): dx and dy hold exactly the floats above
+// the same ray from the host's per-column / per-row tables (tiled pipelines): they hold pixel_dx and pixel_dy of every column and row
 template <bool CAM, bool LENS = false>
 __device__ __forceinline__ Ray camera_ray_xy(const RtwRenderParams& p, int x, int y, int i, PathRng& rng, uint32_t pass = 0u)
 {
-    const float dx = p.cam_dx[x], dy = p.cam_dy[y];
-    const float inv_pixel_radius = 1.0f / (p.width * 4);
-    const float offset_radius = inv_pixel_radius * 0.5f;
-    float ox = (i & 1) ? inv_pixel_radius : 0.0f;
-    float oy = (i & 2) ? inv_pixel_radius : 0.0f;
-    ox += (rng.random() - 0.5f) * offset_radius;
-    oy += (rng.random() - 0.5f) * offset_radius;
-    if (LENS) return lens_ray_from(p, dx + ox, dy + oy, stream_key(p.seed, (uint32_t)(y * p.width + x), (pass * 4u + (uint32_t)i) | RTW_LENS_STREAM));
-    return camera_ray_from<CAM>(p.cam, dx + ox, dy + oy);
+    float a, b;
+    sample_through(p, p.cam_dx[x], p.cam_dy[y], i, rng, a, b);
+    return ray_through<CAM, LENS>(p, a, b, (uint32_t)(y * p.width + x), i, pass);
 }
 
 // 8-bit value of MakePixelColor(LinearToGamma(c)) for one channel: the largest k with thr[k] <= c.

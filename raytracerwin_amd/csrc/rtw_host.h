@@ -4,11 +4,11 @@
 #include <string>
 #include <vector>
 
-#include "rtw_types.h"
+#include "rtw_shared.h"
 
 namespace rtw {
 
-struct Vec3 { float x, y, z; };
+using Vec3 = f3;        // the parser's storage type is the shared float3
 
 struct HostTexture {
     int width = 0, height = 0;

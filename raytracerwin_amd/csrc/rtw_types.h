@@ -117,8 +117,8 @@ inline RtwCamera rtw_default_camera()
     return c;
 }
 
-// What the screen-bin builders (scene_host.cpp build_bins, rtw_build_kernels.h bins_of_leaf) need of a camera, in double: computed once
-// on the host by bins_camera() and handed to both, so that the two routines start from the same numbers.
+// What the screen-bin routine (rtw_shared.h bins_of_leaf, run by scene_host.cpp build_bins and by rtw_build_kernels.h bins_pass_kernel) needs
+// of a camera, in double: computed once on the host by rtw_bins_camera() and handed to either side.
 struct RtwBinsCam {
     double eye[3], right[3], up[3], forward[3];
     double k;                       // 2 * focal * height: a point q (relative to the eye) is seen at x = W/2 - k (q.right) / (q.forward)

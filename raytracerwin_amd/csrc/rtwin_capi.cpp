@@ -639,8 +639,6 @@ inline void set_camera_params(const rtw_scene* scene, RtwRenderParams& p)
 // out before anything is stored, while the camera round writes and reads a slot for every path), 0.61 / 1.05 on unitychan, 0.79 / 0.81 on the
 // reference's default scene -- so the rule is that route; the camera round stays as the cross-check ("lens_route" 1).
 inline bool lens_uses_camera_round(const rtw_context* cx) { return cx->lens_route == 1; }
-// RMath::Random of the path's stream (rtw_device.hip PathRng::random)
-inline float camera_uniform(uint32_t seed, uint32_t pixel, uint32_t sample, uint32_t counter) { return (float)(int32_t)rtw::rand31(seed, pixel, sample, counter) / 2147483648.0f; }
 }  // namespace
 
 int rtw_camera_default(rtw_camera* out)
@@ -703,57 +701,28 @@ static int camera_rays(const rtw_camera* cam, const rtw_lens* lens, int width, i
     if (lens) { if (const char* why = lens_problem(*lens)) return fail(RTW_ERR_INVALID, why); }
     const bool thin = lens && lens->aperture_radius > 0.0f;
     if (thin && pass_index >= (1 << 29)) return fail(RTW_ERR_LIMIT, "pass_index must stay below 2^29 with a lens");
-    const float aspect = (float)width / (float)height;
-    const float inv_pixel_radius = 1.0f / (width * 4);
-    const float offset_radius = inv_pixel_radius * 0.5f;
+    const float aspect = frame_aspect(width, height);
     for (int64_t j = 0; j < n; j++) {
         const int pixel = pixels[j];
         if (pixel < 0 || pixel >= width * height) return fail(RTW_ERR_INVALID, "pixel outside the frame");
-        // ThreadWorker_Render's ray (Src/RayTracerProgram.cpp:141-165) as rtw_device.hip camera_ray builds it
-        const int x = pixel % width, y = pixel / width;
-        const float dx = -(float)(x - width / 2) / (width * 2) * aspect;
-        const float dy = -(float)(y - height / 2) / (height * 2);
-        float ox = (sub_sample & 1) ? inv_pixel_radius : 0.0f;
-        float oy = (sub_sample & 2) ? inv_pixel_radius : 0.0f;
+        // ThreadWorker_Render's ray (Src/RayTracerProgram.cpp:141-165) from the functions the kernels' camera_ray calls (rtw_shared.h)
         const uint32_t sample = (uint32_t)pass_index * 4u + (uint32_t)sub_sample;
-        ox += (camera_uniform(seed, (uint32_t)pixel, sample, 0u) - 0.5f) * offset_radius;
-        oy += (camera_uniform(seed, (uint32_t)pixel, sample, 1u) - 0.5f) * offset_radius;
-        const float a = dx + ox, b = dy + oy;
-        float v[3];
-        for (int k = 0; k < 3; k++) {
-            const float ra = c.right[k] * a, ub = c.up[k] * b, ff = c.forward[k] * c.focal;
-            const float s = ra + ub;
-            v[k] = s + ff;
+        const uint32_t key = stream_key(seed, (uint32_t)pixel, sample);
+        float ox, oy, offset_radius;
+        sample_grid(width, sub_sample, ox, oy, offset_radius);
+        ox = jittered(ox, stream_uniform(key, 0u), offset_radius);
+        oy = jittered(oy, stream_uniform(key, 1u), offset_radius);
+        const f3 v = camera_view(c, pixel_dx(pixel % width, width, aspect) + ox, pixel_dy(pixel / width, height) + oy);
+        f3 o = mk(c.eye[0], c.eye[1], c.eye[2]), d;
+        if (thin) {
+            float lx, ly;
+            lens_point(stream_key(seed, (uint32_t)pixel, sample | RTW_LENS_STREAM), lx, ly);
+            lens_ray(c, lens->aperture_radius, lens->focus_distance, v, lx, ly, o, d);
+        } else {
+            d = normalized(v);
         }
         float* r = rays7 + (size_t)j * 7;
-        if (thin) {
-            // the lens point from its own stream (rtw_device.hip lens_point), then the ray of rtw_device.hip lens_ray_from
-            const uint32_t lsample = sample | RTW_LENS_STREAM;
-            float lx = 0.0f, ly = 0.0f;
-            for (uint32_t t = 0; t < 8u; t++) {
-                const float tx2 = 2.0f * camera_uniform(seed, (uint32_t)pixel, lsample, 2u * t), ty2 = 2.0f * camera_uniform(seed, (uint32_t)pixel, lsample, 2u * t + 1u);
-                const float tx = tx2 - 1.0f, ty = ty2 - 1.0f;
-                const float qx = tx * tx, qy = ty * ty; const float q = qx + qy;
-                if (q <= 1.0f) { lx = tx; ly = ty; break; }
-            }
-            const float s = lens->focus_distance / c.focal;
-            const float lxr = lx * lens->aperture_radius, lyr = ly * lens->aperture_radius;
-            float w[3];
-            for (int k = 0; k < 3; k++) {
-                const float rl = c.right[k] * lxr, ul = c.up[k] * lyr; const float off = rl + ul;
-                const float vs = v[k] * s;
-                r[k] = c.eye[k] + off; w[k] = vs - off;
-            }
-            const float xx = w[0] * w[0], yy = w[1] * w[1], zz = w[2] * w[2];
-            const float sq0 = xx + yy; const float sq = sq0 + zz;
-            const float inv = 1.0f / sqrtf(sq);
-            r[3] = w[0] * inv; r[4] = w[1] * inv; r[5] = w[2] * inv; r[6] = 1000.0f;
-            continue;
-        }
-        const float xx = v[0] * v[0], yy = v[1] * v[1], zz = v[2] * v[2];
-        const float sq0 = xx + yy; const float sq = sq0 + zz;
-        if (!(std::fabs(sq) < FLT_EPSILON)) { const float inv = 1.0f / sqrtf(sq); v[0] *= inv; v[1] *= inv; v[2] *= inv; }
-        r[0] = c.eye[0]; r[1] = c.eye[1]; r[2] = c.eye[2]; r[3] = v[0]; r[4] = v[1]; r[5] = v[2]; r[6] = 1000.0f;
+        r[0] = o.x; r[1] = o.y; r[2] = o.z; r[3] = d.x; r[4] = d.y; r[5] = d.z; r[6] = 1000.0f;
     }
     return RTW_OK;
 }
@@ -987,34 +956,44 @@ int rtw_scene_mesh_flat(const rtw_scene* scene, int shape, int level, float* box
     return m.flat_n[level];
 }
 
+// The screen bins of mesh s from whichever side built the mesh.  On the device (what the renderer uses): d_off / d_ent are the caller's
+// (hipFree) and `off` is their offsets' copy; on the host: `off` and `ent`, d_off = d_ent = null.  ok false: this mesh gets no bins.
+namespace {
+struct MeshBins { bool ok = false; std::vector<uint32_t> off, ent; uint32_t *d_off = nullptr, *d_ent = nullptr; };
+int mesh_bins(const rtw_scene* scene, size_t s, int width, int height, int bin_w, int bin_h, MeshBins& b)
+{
+    if (!(scene->ctx && scene->ctx->device_build && scene->d_nodes_of.size() > s && scene->d_nodes_of[s])) {
+        b.ok = rtw::build_bins(*scene->meshes[s], scene->camera, width, height, bin_w, bin_h, b.off, b.ent);
+        return RTW_OK;
+    }
+    if (width <= 0 || height <= 0 || bin_w <= 0 || bin_h <= 0) return fail(RTW_ERR_INVALID, "bad bin geometry");
+    HIP_TRY(hipSetDevice(scene->ctx->device));
+    b.off.resize((size_t)((width + bin_w - 1) / bin_w) * (size_t)((height + bin_h - 1) / bin_h) + 1);
+    int has = 0;
+    const hipError_t be = (hipError_t)rtw::device_build_bins(scene->d_nodes_of[s], scene->d_tris_of[s], (int)scene->meshes[s]->nodes.size(), scene->camera, width, height, bin_w, bin_h,
+                                                             &b.d_off, &b.d_ent, b.off.data(), &has, scene->ctx->stream);
+    if (be != hipSuccess) return hip_fail(be, "device bins build");
+    b.ok = has != 0;
+    return RTW_OK;
+}
+}  // namespace
+
 int rtw_scene_mesh_bins(const rtw_scene* scene, int shape, int width, int height, int bin_w, int bin_h,
                         uint32_t* offsets, int64_t max_offsets, uint32_t* entries, int64_t max_entries, int64_t* counts2)
 {
     if (!scene || shape < 0 || shape >= (int)scene->meshes.size()) return fail(RTW_ERR_INVALID, "bad shape index");
     if (!scene->committed) return fail(RTW_ERR_STATE, "scene not committed");
     if (!counts2) return fail(RTW_ERR_INVALID, "null argument");
-    std::vector<uint32_t> off, ent;
-    bool ok;
     if (scene->has_lens()) { counts2[0] = 0; counts2[1] = 0; return 0; }       // rays that start all over the aperture: no mesh gets bins (scene_bins)
-    if (scene->ctx && scene->ctx->device_build && scene->d_nodes_of.size() > (size_t)shape && scene->d_nodes_of[(size_t)shape]) {
-        // what the renderer uses: the lists built on the device
-        if (width <= 0 || height <= 0 || bin_w <= 0 || bin_h <= 0) return fail(RTW_ERR_INVALID, "bad bin geometry");
-        HIP_TRY(hipSetDevice(scene->ctx->device));
-        const size_t n_bins = (size_t)((width + bin_w - 1) / bin_w) * (size_t)((height + bin_h - 1) / bin_h);
-        off.resize(n_bins + 1);
-        uint32_t *d_off = nullptr, *d_ent = nullptr; int has = 0;
-        const hipError_t be = (hipError_t)rtw::device_build_bins(scene->d_nodes_of[(size_t)shape], scene->d_tris_of[(size_t)shape], (int)scene->meshes[(size_t)shape]->nodes.size(),
-                                                                 scene->camera, width, height, bin_w, bin_h, &d_off, &d_ent, off.data(), &has, scene->ctx->stream);
-        if (be != hipSuccess) return hip_fail(be, "device bins build");
-        ok = has != 0;
-        if (ok) {
-            ent.resize(off.back() ? off.back() : 1, 0u);
-            const hipError_t ce = off.back() ? hipMemcpy(ent.data(), d_ent, (size_t)off.back() * 4, hipMemcpyDeviceToHost) : hipSuccess;
-            (void)hipFree(d_off); (void)hipFree(d_ent);
-            if (ce != hipSuccess) return hip_fail(ce, "bins read-back");
-        }
-    } else {
-        ok = rtw::build_bins(*scene->meshes[(size_t)shape], scene->camera, width, height, bin_w, bin_h, off, ent);
+    MeshBins mb;
+    const int rc = mesh_bins(scene, (size_t)shape, width, height, bin_w, bin_h, mb); if (rc != RTW_OK) return rc;
+    std::vector<uint32_t>& off = mb.off; std::vector<uint32_t>& ent = mb.ent;
+    const bool ok = mb.ok;
+    if (ok && mb.d_ent) {                // built on the device: read the entries back
+        ent.resize(off.back() ? off.back() : 1, 0u);
+        const hipError_t ce = off.back() ? hipMemcpy(ent.data(), mb.d_ent, (size_t)off.back() * 4, hipMemcpyDeviceToHost) : hipSuccess;
+        (void)hipFree(mb.d_off); (void)hipFree(mb.d_ent);
+        if (ce != hipSuccess) return hip_fail(ce, "bins read-back");
     }
     counts2[0] = ok ? (int64_t)off.size() : 0; counts2[1] = ok ? (int64_t)off.back() : 0;
     if (!ok) return 0;                   // this mesh gets no bins (not wholly in front of the camera, or the frame does not tile)
@@ -1308,35 +1287,28 @@ static int scene_bins(rtw_scene* scene, int width, int height, int bin_w, int bi
     const size_t n_bins = (size_t)((width + bin_w - 1) / bin_w) * (size_t)((height + bin_h - 1) / bin_h);
     std::vector<uint32_t> weight(n_bins, 0u);
     for (size_t s = 0; s < scene->meshes.size(); s++) {
-        std::vector<uint32_t> off, ent;
         h[s].off = nullptr; h[s].ent = nullptr;
         if (scene->meshes[s]->kind != RTW_SHAPE_MESH) { for (auto& w : weight) w += 1u; continue; }      // tested by every sample of every tile
         // a lens: the projection from `eye` no longer bounds what a tile's rays can meet -> no bins, every tile of a scene with a mesh is busy
         if (scene->has_lens()) { for (auto& w : weight) w += 1000u; continue; }
-        if (scene->ctx->device_build && scene->d_nodes_of.size() > s && scene->d_nodes_of[s]) {
-            // the same lists from the device: counted, scanned, filled and sorted there (rtw_build_kernels.h); only the offsets come back (tile weights)
-            off.resize(n_bins + 1);
-            uint32_t *d_off = nullptr, *d_ent = nullptr; int has = 0;
-            const hipError_t be = (hipError_t)rtw::device_build_bins(scene->d_nodes_of[s], scene->d_tris_of[s], (int)scene->meshes[s]->nodes.size(), scene->camera, width, height, bin_w, bin_h,
-                                                                     &d_off, &d_ent, off.data(), &has, scene->ctx->stream);
-            if (be != hipSuccess) return hip_fail(be, "device bins build");
-            if (!has) { for (auto& w : weight) w += 1000u; continue; }
-            scene->allocs.push_back(d_off); scene->allocs.push_back(d_ent);
-            for (size_t b = 0; b < n_bins; b++) weight[b] += off[b + 1] - off[b];
-            h[s].off = d_off; h[s].ent = d_ent;
+        // device-built lists are counted, scanned, filled and sorted there (rtw_build_kernels.h): only the offsets come back (tile weights)
+        MeshBins mb;
+        int rc = mesh_bins(scene, s, width, height, bin_w, bin_h, mb); if (rc != RTW_OK) return rc;
+        if (!mb.ok) { for (auto& w : weight) w += 1000u; continue; }
+        for (size_t b = 0; b < n_bins; b++) weight[b] += mb.off[b + 1] - mb.off[b];
+        if (mb.d_off) {
+            scene->allocs.push_back(mb.d_off); scene->allocs.push_back(mb.d_ent);
+            h[s].off = mb.d_off; h[s].ent = mb.d_ent;
             continue;
         }
-        if (!rtw::build_bins(*scene->meshes[s], scene->camera, width, height, bin_w, bin_h, off, ent)) { for (auto& w : weight) w += 1000u; continue; }
-        for (size_t b = 0; b < n_bins; b++) weight[b] += off[b + 1] - off[b];
-        int rc;
-        if ((rc = upload(scene, off, &h[s].off)) != RTW_OK) return rc;
-        if ((rc = upload(scene, ent, &h[s].ent)) != RTW_OK) return rc;
+        if ((rc = upload(scene, mb.off, &h[s].off)) != RTW_OK) return rc;
+        if ((rc = upload(scene, mb.ent, &h[s].ent)) != RTW_OK) return rc;
     }
     // the camera's per-column dx and per-row dy, as ThreadWorker_Render computes them for every pixel (Src/RayTracerProgram.cpp:141-142)
     std::vector<float> dx((size_t)width), dy((size_t)height);
-    const float aspect = (float)width / (float)height;
-    for (int x = 0; x < width; x++) dx[(size_t)x] = -(float)(x - width / 2) / (width * 2) * aspect;
-    for (int y = 0; y < height; y++) dy[(size_t)y] = -(float)(y - height / 2) / (height * 2);
+    const float aspect = frame_aspect(width, height);
+    for (int x = 0; x < width; x++) dx[(size_t)x] = pixel_dx(x, width, aspect);
+    for (int y = 0; y < height; y++) dy[(size_t)y] = pixel_dy(y, height);
     const RtwBinsDev* d = nullptr; const float* ddx = nullptr; const float* ddy = nullptr;
     rtw_scene::BinSet bsnew;
     int rc = upload(scene, h, &d); if (rc != RTW_OK) return rc;

@@ -21,23 +21,6 @@ namespace rtw {
 
 namespace {
 
-inline Vec3 sub(Vec3 a, Vec3 b) { return { a.x - b.x, a.y - b.y, a.z - b.z }; }
-inline Vec3 add(Vec3 a, Vec3 b) { return { a.x + b.x, a.y + b.y, a.z + b.z }; }
-inline Vec3 cross(Vec3 a, Vec3 b) { return { a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x }; }
-inline float dot(Vec3 a, Vec3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-inline bool near_zero(float a) { return std::fabs(a) < FLT_EPSILON; }   // FLT_EQUAL_ZERO, Src/MathHelper.h:12
-
-// RVec3::GetNormalizedVec3 (Src/RVector.h:169-183): tiny vectors are returned un-normalised
-inline Vec3 normalized(Vec3 v)
-{
-    float sq = v.x * v.x + v.y * v.y + v.z * v.z;
-    if (!near_zero(sq)) {
-        float inv = 1.0f / std::sqrt(sq);
-        v.x *= inv; v.y *= inv; v.z *= inv;
-    }
-    return v;
-}
-
 // --- line tokenising ------------------------------------------------------------------
 // "keyword" = text before the first blank (Src/MeshShape.cpp:23-36)
 std::string keyword_of(const std::string& line)
@@ -234,7 +217,7 @@ struct TreeBuilder {
     }
     Vec3 centroid(const BuildRef& t) const
     {
-        const Vec3 s = add(add(m.points[(size_t)t.a], m.points[(size_t)t.b]), m.points[(size_t)t.c]);
+        const Vec3 s = (m.points[(size_t)t.a] + m.points[(size_t)t.b]) + m.points[(size_t)t.c];
         return { s.x / 3.0f, s.y / 3.0f, s.z / 3.0f };
     }
 
@@ -261,7 +244,7 @@ struct TreeBuilder {
             add_leaf_records(refs[0]);
         } else {
             Vec3 mean = { 0, 0, 0 };
-            for (const BuildRef& t : refs) mean = add(mean, centroid(t));
+            for (const BuildRef& t : refs) mean = mean + centroid(t);
             const float n = (float)refs.size();
             mean.x /= n; mean.y /= n; mean.z /= n;
             const int axis = split_axis(lo, hi);
@@ -286,23 +269,11 @@ struct TreeBuilder {
 
     void add_leaf_records(const BuildRef& t)
     {
-        const Vec3 p0 = m.points[(size_t)t.a], p1 = m.points[(size_t)t.b], p2 = m.points[(size_t)t.c];
-        // the reference recomputes this per test (Src/RRay.cpp:138-145); it only depends on the triangle
-        const Vec3 n = normalized(cross(sub(p1, p0), sub(p2, p0)));
-        RtwTri r;
-        r.p0x = p0.x; r.p0y = p0.y; r.p0z = p0.z; r.nx = n.x;
-        r.p1x = p1.x; r.p1y = p1.y; r.p1z = p1.z; r.ny = n.y;
-        r.p2x = p2.x; r.p2y = p2.y; r.p2z = p2.z; r.nz = n.z;
-        r.d1 = dot(n, p0); r.orig = t.index; r.pad0 = r.pad1 = 0;
-        m.tris.push_back(r);
+        m.tris.push_back(tri_record(m.points[(size_t)t.a], m.points[(size_t)t.b], m.points[(size_t)t.c], t.index));
         const size_t v = (size_t)t.index * 3;
-        const Vec3 n0 = m.normals[(size_t)m.normal_idx[v]], n1 = m.normals[(size_t)m.normal_idx[v + 1]], n2 = m.normals[(size_t)m.normal_idx[v + 2]];
-        const Vec3 t0 = m.texcoords[(size_t)m.texcoord_idx[v]], t1 = m.texcoords[(size_t)m.texcoord_idx[v + 1]], t2 = m.texcoords[(size_t)m.texcoord_idx[v + 2]];
-        RtwShade s;
-        s.n0x = n0.x; s.n0y = n0.y; s.n0z = n0.z; s.n1x = n1.x; s.n1y = n1.y; s.n1z = n1.z; s.n2x = n2.x; s.n2y = n2.y; s.n2z = n2.z;
-        s.u0 = t0.x; s.v0 = t0.y; s.u1 = t1.x; s.v1 = t1.y; s.u2 = t2.x; s.v2 = t2.y;
-        s.material = m.poly_material[(size_t)t.index];
-        m.shade.push_back(s);
+        m.shade.push_back(shade_record(m.normals[(size_t)m.normal_idx[v]], m.normals[(size_t)m.normal_idx[v + 1]], m.normals[(size_t)m.normal_idx[v + 2]],
+                                       m.texcoords[(size_t)m.texcoord_idx[v]], m.texcoords[(size_t)m.texcoord_idx[v + 1]], m.texcoords[(size_t)m.texcoord_idx[v + 2]],
+                                       m.poly_material[(size_t)t.index]));
     }
 };
 
@@ -310,10 +281,9 @@ struct TreeBuilder {
 
 void triangle_plane(const float p0[3], const float p1[3], const float p2[3], float n[3], float* d1)
 {
-    const Vec3 a = { p0[0], p0[1], p0[2] }, b = { p1[0], p1[1], p1[2] }, c = { p2[0], p2[1], p2[2] };
-    const Vec3 nn = normalized(cross(sub(b, a), sub(c, a)));
-    n[0] = nn.x; n[1] = nn.y; n[2] = nn.z;
-    *d1 = dot(nn, a);
+    const RtwTri r = tri_record(mk(p0[0], p0[1], p0[2]), mk(p1[0], p1[1], p1[2]), mk(p2[0], p2[1], p2[2]), 0);
+    n[0] = r.nx; n[1] = r.ny; n[2] = r.nz;
+    *d1 = r.d1;
 }
 
 void build_tree(HostMesh& m)
@@ -366,17 +336,10 @@ void build_tnodes(HostMesh& m, int top_budget)
             for (int j = i + 1; j < m.nodes[(size_t)i].skip; j++) order.push_back(j);      // the subtree below i, preorder
         }
     }
-    std::vector<int> place((size_t)n + 1, n);
+    std::vector<int32_t> place((size_t)n + 1, n);
     for (int k = 0; k < n; k++) place[(size_t)order[(size_t)k]] = k;
     m.tnodes.resize((size_t)n);
-    for (int k = 0; k < n; k++) {
-        const RtwNode& src = m.nodes[(size_t)order[(size_t)k]];
-        RtwPNode t;
-        t.min_x = src.min_x; t.max_x = src.max_x; t.min_y = src.min_y; t.max_y = src.max_y; t.min_z = src.min_z; t.max_z = src.max_z;
-        t.skip = place[(size_t)src.skip];
-        t.link = src.tri >= 0 ? src.tri : -1 - place[(size_t)order[(size_t)k] + 1];
-        m.tnodes[(size_t)k] = t;
-    }
+    for (int i = 0; i < n; i++) m.tnodes[(size_t)place[(size_t)i]] = link_record(m.nodes[(size_t)i], place.data(), i);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -396,122 +359,33 @@ void build_flat(HostMesh& m)
         m.flat[l].assign((size_t)6 * (size_t)m.flat_pad[l], 0.0f);
         n = (n + 15) / 16;
     }
-    // entry i of a level = six floats (min x, max x, min y, max y, min z, max z); c = 0..2 min x/y/z, 3..5 max x/y/z
-    auto at = [&](int l, int c, int i) -> float& { return m.flat[l][(size_t)i * 6 + (size_t)(c < 3 ? 2 * c : 2 * (c - 3) + 1)]; };
-    for (const RtwNode& nd : m.nodes) {
-        if (nd.tri < 0) continue;
-        at(0, 0, nd.tri) = nd.min_x; at(0, 1, nd.tri) = nd.min_y; at(0, 2, nd.tri) = nd.min_z;
-        at(0, 3, nd.tri) = nd.max_x; at(0, 4, nd.tri) = nd.max_y; at(0, 5, nd.tri) = nd.max_z;
-    }
-    for (int l = 1; l < 3; l++) {
-        for (int k = 0; k < m.flat_n[l]; k++) {
-            for (int c = 0; c < 3; c++) {
-                float lo = FLT_MAX, hi = -FLT_MAX;
-                for (int i = 16 * k; i < 16 * k + 16 && i < m.flat_n[l - 1]; i++) {
-                    if (at(l - 1, c, i) < lo) lo = at(l - 1, c, i);
-                    if (at(l - 1, c + 3, i) > hi) hi = at(l - 1, c + 3, i);
-                }
-                at(l, c, k) = lo; at(l, c + 3, k) = hi;
-            }
-        }
-    }
+    for (const RtwNode& nd : m.nodes) if (nd.tri >= 0) flat_leaf_entry(nd, &m.flat[0][(size_t)nd.tri * 6]);
+    for (int l = 1; l < 3; l++)
+        for (int k = 0; k < m.flat_n[l]; k++) flat_union_entry(m.flat[l - 1].data(), m.flat_n[l - 1], m.flat[l].data(), k);
 }
 
 // ---------------------------------------------------------------------------------------
-// Screen-space bins of the scene's camera.  Pixel (x, y), sub-sample offset (ox, oy) looks along
-// (dx + ox) right + (dy + oy) up + focal forward with dx = -(x - W/2) / (2W) * (W/H), dy = -(y - H/2) / (2H) (Src/RayTracerProgram.cpp:141-165),
-// so a point q (relative to the eye, depth = q.forward > 0) is seen at x = W/2 - 2 focal H (q.right) / depth, y = H/2 - 2 focal H (q.up) / depth
-// (the offsets move a sample by less than half a pixel).  For the reference's own camera -- eye (0, 0, 7), the axes, focal 0.5 -- these are
-// x = W/2 + H q.x / q.z, y = H/2 + H q.y / q.z with the same roundings.  A bin lists the leaves whose triangle a camera ray of the bin's pixels could
-// ACCEPT: the triangle faces the camera (the reference's own float test, identical for every camera ray) and its projection,
-// grown by a one-pixel margin, touches the bin (separating-axis test against the bin's rectangle).  A leaf left out would have
-// been box- or triangle-tested by the reference and rejected, which changes no result; the kernel still runs the reference's
-// box and triangle tests on every listed leaf, per ray.
+// Screen-space bins of the scene's camera: rtw_shared.h bins_of_leaf, the routine the device's bins_pass_kernel runs, leaf by leaf,
+// then the lists in CSR form.
 // ---------------------------------------------------------------------------------------
 bool build_bins(const HostMesh& m, const RtwCamera& camera, int width, int height, int bin_w, int bin_h, std::vector<uint32_t>& off, std::vector<uint32_t>& ent)
 {
     off.clear(); ent.clear();
     if (width <= 0 || height <= 0 || bin_w <= 0 || bin_h <= 0) return false;
-    const RtwBinsCam cam = rtw_bins_camera(camera, width, height);
-    if (!cam.ok) return false;
-    const int bx = (width + bin_w - 1) / bin_w, by = (height + bin_h - 1) / bin_h;      // the bins at the right / bottom edge may be partial
-    const double cx = (double)(width / 2), cy = (double)(height / 2);
-    // A sub-sample looks through a point up to 1.25 / (4 W) off its pixel centre in dx and dy (Src/RayTracerProgram.cpp:147-162), i.e.
-    // 1.25 H / (2 W) PIXELS (a pixel is 1 / (2 H) wide in those units): under half a pixel for landscape frames, several pixels for tall
-    // narrow ones.  The margin covers that plus a pixel of slack, plus what a basis that is orthonormal only to rounding can move a
-    // projection by (rtw_types.h rtw_bins_camera: nothing for the default camera).
-    const double margin = cam.margin;
+    RtwBinsGeom g;
+    g.width = width; g.height = height; g.bin_w = bin_w; g.bin_h = bin_h;
+    g.bx = (width + bin_w - 1) / bin_w; g.by = (height + bin_h - 1) / bin_h;
+    g.cam = rtw_bins_camera(camera, width, height); g.margin = g.cam.margin;
+    if (!g.cam.ok) return false;
     struct Item { int node, bin; };
     std::vector<Item> items;
     items.reserve(m.tris.size() * 4);
     for (size_t i = 0; i < m.nodes.size(); i++) {
         const RtwNode& nd = m.nodes[i];
         if (nd.tri < 0) continue;
-        // all eight corners of the leaf's box in front of the eye (depth = q . forward > 0.01), else no bins for this mesh
-        for (int c = 0; c < 8; c++) {
-            const double qx = (double)((c & 1) ? nd.max_x : nd.min_x) - cam.eye[0], qy = (double)((c & 2) ? nd.max_y : nd.min_y) - cam.eye[1],
-                         qz = (double)((c & 4) ? nd.max_z : nd.min_z) - cam.eye[2];
-            const double depth = qx * cam.forward[0] + qy * cam.forward[1] + qz * cam.forward[2];
-            if (!(depth > 0.01)) return false;
-        }
-        const RtwTri& t = m.tris[(size_t)nd.tri];
-        // Every camera ray starts at the eye: the reference's first rejection, "origin behind the triangle's plane"
-        // (d2 = N.O - N.P0 < 0, Src/RRay.cpp:156-160), is the same float computation for all of them, so a triangle that
-        // fails it is accepted by no camera ray and needs no bin at all.
-        {
-            const float ox = cam.eye_f[0], oy = cam.eye_f[1], oz = cam.eye_f[2];
-            const float d0 = t.nx * ox + t.ny * oy + t.nz * oz;
-            const float d2 = d0 - t.d1;
-            if (d2 < 0) continue;
-        }
-        // the triangle's projection (an accepted hit lies inside the triangle, so its pixel lies inside this projection)
-        const double vx[3] = { t.p0x, t.p1x, t.p2x }, vy[3] = { t.p0y, t.p1y, t.p2y }, vz[3] = { t.p0z, t.p1z, t.p2z };
-        double sx[3], sy[3];
-        bool finite = true;
-        for (int k = 0; k < 3; k++) {
-            const double qx = vx[k] - cam.eye[0], qy = vy[k] - cam.eye[1], qz = vz[k] - cam.eye[2];
-            const double depth = qx * cam.forward[0] + qy * cam.forward[1] + qz * cam.forward[2];
-            const double qr = qx * cam.right[0] + qy * cam.right[1] + qz * cam.right[2], qu = qx * cam.up[0] + qy * cam.up[1] + qz * cam.up[2];
-            sx[k] = cx - cam.k * qr / depth; sy[k] = cy - cam.k * qu / depth;
-            finite = finite && sx[k] == sx[k] && sy[k] == sy[k] && std::fabs(sx[k]) < 1e12 && std::fabs(sy[k]) < 1e12;
-        }
-        if (!finite) return false;
-        const double xa = std::min(sx[0], std::min(sx[1], sx[2])), xb = std::max(sx[0], std::max(sx[1], sx[2]));
-        const double ya = std::min(sy[0], std::min(sy[1], sy[2])), yb = std::max(sy[0], std::max(sy[1], sy[2]));
-        double fx0 = std::floor(xa - margin), fx1 = std::ceil(xb + margin), fy0 = std::floor(ya - margin), fy1 = std::ceil(yb + margin);
-        if (fx1 < 0 || fy1 < 0 || fx0 > width - 1 || fy0 > height - 1) continue;      // off screen
-        if (fx0 < 0) fx0 = 0;
-        if (fy0 < 0) fy0 = 0;
-        if (fx1 > width - 1) fx1 = width - 1;
-        if (fy1 > height - 1) fy1 = height - 1;
-        const int bx0 = (int)fx0 / bin_w, bx1 = (int)fx1 / bin_w, by0 = (int)fy0 / bin_h, by1 = (int)fy1 / bin_h;
-        // edges of the projected triangle with outward normals (skipped when the projection is degenerate)
-        const double area2 = (sx[1] - sx[0]) * (sy[2] - sy[0]) - (sx[2] - sx[0]) * (sy[1] - sy[0]);
-        const double scale = std::fabs(xb - xa) + std::fabs(yb - ya) + 1.0;
-        const bool use_edges = std::fabs(area2) > 1e-9 * scale * scale;
-        for (int yb_ = by0; yb_ <= by1; yb_++) {
-            for (int xb_ = bx0; xb_ <= bx1; xb_++) {
-                bool separated = false;
-                if (use_edges) {
-                    // the bin's pixels, grown by the margin (a sample looks through a point less than half a pixel off its pixel)
-                    const double rx0 = (double)(xb_ * bin_w) - margin, rx1 = (double)(xb_ * bin_w + bin_w - 1) + margin;
-                    const double ry0 = (double)(yb_ * bin_h) - margin, ry1 = (double)(yb_ * bin_h + bin_h - 1) + margin;
-                    for (int e = 0; e < 3 && !separated; e++) {
-                        const int a = e, b2 = (e + 1) % 3, c = (e + 2) % 3;
-                        double nx = sy[b2] - sy[a], ny = -(sx[b2] - sx[a]);            // normal of edge a -> b
-                        if (nx * (sx[c] - sx[a]) + ny * (sy[c] - sy[a]) > 0) { nx = -nx; ny = -ny; }      // pointing away from the third vertex
-                        const double len = std::sqrt(nx * nx + ny * ny);
-                        if (!(len > 0)) continue;
-                        // the rectangle's corner that is deepest along -n: if even it is outside, the whole rectangle is
-                        const double px = nx > 0 ? rx0 : rx1, py = ny > 0 ? ry0 : ry1;
-                        if ((nx * (px - sx[a]) + ny * (py - sy[a])) / len > 1e-6) separated = true;
-                    }
-                }
-                if (!separated) items.push_back({ (int)i, yb_ * bx + xb_ });
-            }
-        }
+        if (!bins_of_leaf(nd, m.tris[(size_t)nd.tri], g, [&](int bin) { items.push_back({ (int)i, bin }); })) return false;
     }
-    off.assign((size_t)bx * (size_t)by + 1, 0u);
+    off.assign((size_t)g.bx * (size_t)g.by + 1, 0u);
     for (const Item& it : items) off[(size_t)it.bin + 1]++;
     for (size_t i = 1; i < off.size(); i++) off[i] += off[i - 1];
     ent.assign(off.back() ? off.back() : 1, 0u);
@@ -523,20 +397,9 @@ bool build_bins(const HostMesh& m, const RtwCamera& camera, int width, int heigh
 // ---------------------------------------------------------------------------------------
 // random stream + host-generated tables
 // ---------------------------------------------------------------------------------------
-namespace {
-inline uint32_t mix32(uint32_t x) { x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16; return x; }
-inline uint32_t stream_key(uint32_t seed, uint32_t pixel, uint32_t sample)
-{
-    uint32_t h = mix32(seed ^ 0x9E3779B9u);
-    h = mix32(h + pixel);
-    return mix32(h + sample);
-}
-inline float uniform_from(uint32_t r31) { return (float)(int32_t)r31 / 2147483648.0f; }   // (float)rand() / RAND_MAX
-}  // namespace
-
 uint32_t rand31(uint32_t seed, uint32_t pixel, uint32_t sample, uint32_t counter)
 {
-    return mix32(stream_key(seed, pixel, sample) + counter) >> 1;
+    return stream_draw31(stream_key(seed, pixel, sample), counter);
 }
 
 // entry i of the table RMath::InitPseudoRandomUnitVector would fill (Src/Math.cpp:24-31,
@@ -544,8 +407,8 @@ uint32_t rand31(uint32_t seed, uint32_t pixel, uint32_t sample, uint32_t counter
 void unit_table_entry(uint32_t index, float out3[3])
 {
     const uint32_t key = stream_key(RTW_TABLE_SEED, 0xFFFFFFFFu, 0xFFFFFFFFu);
-    const float r1 = uniform_from(mix32(key + 2u * index) >> 1);
-    const float r2 = uniform_from(mix32(key + 2u * index + 1u) >> 1);
+    const float r1 = stream_uniform(key, 2u * index);
+    const float r2 = stream_uniform(key, 2u * index + 1u);
     const float t1 = 2.0f * 3.1415926f * r1;
     const float t2 = acosf(1.0f - 2.0f * r2);
     const float sin_t2 = sinf(t2);

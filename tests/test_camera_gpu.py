@@ -176,3 +176,30 @@ def test_two_ranks_with_the_same_camera_compose_the_one_rank_frame(ctx, oracle_m
         assert equal(one, CS.oracle_frame(oracle_mod, asset, CS.MIXED, CS.cam13(R, "below"), W, H, 2, DEPTH, n_passes=3, seed=SEED))
     finally:
         s.close()
+
+
+BINS_POSES = ["offaxis", "below", "narrow", "wide"]
+
+
+@pytest.mark.parametrize("bin_w,bin_h", [(16, 4), (32, 2)])
+def test_device_built_bins_equal_host_built_bins_for_general_poses(ctx, oracle_mod, bin_w, bin_h):
+    """The screen bins of a mesh are the same lists whichever side built them (rtw_shared.h bins_of_leaf runs on both): exact equality of
+    the offsets and the entries for general poses, a non-empty list for at least three of the four, and "no bins" from both sides for
+    the pose inside the mesh's bounds."""
+    W, H = 96, 54
+    got = {}
+    try:
+        for dev in (1, 0):
+            ctx.set_option("device_build", dev)
+            for pose in BINS_POSES + ["inside"]:
+                s = scene_with(ctx, oracle_mod, CS.TORUS, pose)
+                got[dev, pose] = s.mesh_bins(W, H, bin_w, bin_h, 0)
+                s.close()
+    finally:
+        ctx.set_option("device_build", 1)
+    for pose in BINS_POSES:
+        d, h = got[1, pose], got[0, pose]
+        assert d is not None and h is not None, pose
+        assert (d[0] == h[0]).all() and len(d[1]) == len(h[1]) and (d[1] == h[1]).all(), pose
+    assert sum(1 for pose in BINS_POSES if len(got[0, pose][1]) > 0) >= 3
+    assert got[1, "inside"] is None and got[0, "inside"] is None
