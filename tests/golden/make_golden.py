@@ -36,6 +36,7 @@ MATERIALS = {
                 (D, (0.95, 0.75, 0.1), 0, 0, 0), (EM, (0.475, 0.375, 0.05), 0, 0, 0)],
     "null": [(NU, (0, 0, 0), 0, 0, 0)],
     "partial": [(D, (0.5, 0.0, 0.2), 0, 0, 0)],
+    "combine_d16": [(CO, (0, 0, 0), 0, 1, 2), (EM, (0.3, 0.2, 0.1), 0, 0, 0), (D, (2.5, 2.2, 2.0), 0, 0, 0)],     # tests/material_support.py DEPTH16_TREE
 }
 
 
@@ -530,6 +531,48 @@ def golden_scene_frame(name, tag, W, Hh, ns, depth, preview, seed, pass0, npass,
                         argb=np.fromfile(fp + ".argb.u32", np.uint32))
 
 
+def golden_materials(tmp):
+    """The material trees of tests/material_support.py marked `ref`, through the reference's own BounceViewRay / PreviewColor: per tree
+    matedge_<name>.npz with a `raytrace` record (TorusKnot, depth 6, the rays and keys of matedge_rays.npz, which all trees share), a 48 x 27 frame
+    (2 sub-samples, depth 5, one pass) and the same frame in the preview version; scene "matedge" (three Combine trees on analytic shapes); and the
+    depth-16 frames.  A generator of its own: no other fixture's draw moves."""
+    import material_support as MS
+    rng = np.random.default_rng(20261023)
+    bounds = np.load(os.path.join(OUT, "mesh_%s.npz" % MS.MESH))["shape_bounds"]
+    rays = make_rays(bounds, 134, rng)
+    depth, seed, RW, RH = 6, 4242, 1920, 1080
+    keys = np.c_[rng.integers(0, RW * RH, len(rays)), rng.integers(0, 8, len(rays))].astype(np.uint32)
+    np.savez_compressed(os.path.join(OUT, "matedge_rays.npz"), mesh=MS.MESH, rays=rays, keys=keys, params=np.array([depth, seed, RW, RH], np.int64))
+    mp, rp, kp, op, fp = [os.path.join(tmp, f) for f in ("mat.bin", "rays.bin", "keys.bin", "rt.bin", "frame")]
+    rays.tofile(rp)
+    keys.tofile(kp)
+    W, Hh, ns, fdepth = MS.FRAME
+    for name in MS.REF_TREES:
+        arr = O.materials(MS.TREES[name][0])
+        arr.tofile(mp)
+        run(["raytrace", obj_path(MS.MESH), mp, rp, kp, len(rays), depth, 0, seed, RW, RH, op])
+        rgb = np.fromfile(op, np.float32).reshape(-1, 3)
+        run(["frame", obj_path(MS.MESH), mp, W, Hh, ns, fdepth, 0, MS.SEED, 0, 1, 0, W * Hh - 1, fp])
+        accum, argb = np.fromfile(fp + ".accum.f32", np.float32).reshape(-1, 4), np.fromfile(fp + ".argb.u32", np.uint32)
+        run(["frame", obj_path(MS.MESH), mp, W, Hh, ns, fdepth, 1, MS.SEED, 0, 1, 0, W * Hh - 1, fp])
+        np.savez_compressed(os.path.join(OUT, "matedge_%s.npz" % name), mesh=MS.MESH, material=arr, rgb=rgb,
+                            params=np.array([W, Hh, ns, fdepth, 0, MS.SEED, 0, 1], np.int64), accum=accum, argb=argb,
+                            preview_argb=np.fromfile(fp + ".argb.u32", np.uint32))
+    golden_scene_frame("matedge_d5", "matedge", 64, 36, 2, 5, 0, MS.SEED, 0, 1, tmp)
+    golden_scene_frame("matedge_preview", "matedge", 64, 36, 2, 5, 1, MS.SEED, 0, 1, tmp)
+    golden_depth16(tmp)
+
+
+def golden_depth16(tmp):
+    """depth 16 = RTW_MAX_BOUNCE: the mirror (its paths end long before: fewer than 8 levels on this mesh), and MS.DEPTH16_TREE, a
+    combine(Emissive, Diffuse) whose surviving ray is the incoming one, so that every path that hits the mesh runs to the last level"""
+    import material_support as MS
+    d16 = MS.DEPTH16
+    golden_frame("torus_mirror_d16", d16["mesh"], "mirror", d16["W"], d16["H"], d16["ns"], d16["depth"], 0, d16["seed"], 0, 1, tmp)
+    assert MATERIALS["combine_d16"] == MS.DEPTH16_TREE
+    golden_frame("torus_combine_d16", d16["mesh"], "combine_d16", d16["W"], d16["H"], d16["ns"], d16["depth"], 0, d16["seed"], 0, 1, tmp)
+
+
 def main_scenes(tmp, rng, bounds):
     """multi-shape scenes: RSphere / RPlane / RCapsule beside meshes (tests/scenes.py)"""
     for tag in ("default_nofuzz", "quirk", "shapes", "room", "tris"):
@@ -570,6 +613,10 @@ def main():
             bounds = {n: np.load(os.path.join(OUT, "mesh_%s.npz" % n))["shape_bounds"] for n in ("TorusKnot", "BlenderMonkey", "unitychan")}
             main_scenes(tmp, rng, bounds)
         return
+    if "--materials-only" in sys.argv:     # add the material-tree fixtures (tests/test_material_*.py) without regenerating the others
+        with tempfile.TemporaryDirectory() as tmp:
+            golden_materials(tmp)
+        return
     with tempfile.TemporaryDirectory() as tmp:
         bounds = {}
         for name in ("TorusKnot", "BlenderMonkey", "unitychan"):
@@ -599,6 +646,7 @@ def main():
         golden_misc(tmp)
         golden_edges(tmp)
         golden_oddtex(tmp)
+        golden_materials(tmp)
     total = sum(os.path.getsize(os.path.join(OUT, f)) for f in os.listdir(OUT) if f.endswith(".npz"))
     print("golden fixtures written: %.2f MB" % (total / 1e6))
 

@@ -142,8 +142,20 @@ def edges_scene(negative=False):
     ] + ([("sphere", (0.0, 3.0, 0.0), -0.5, diffuse((0.9, 0.3, 0.3)))] if negative else [])            # 15: only the radius's square and the box use it
 
 
+def matedge_scene():
+    """Three of the Combine trees of tests/material_support.py (co_em_d, co_co, co_d_d) on analytic shapes: an emissive A operand (the incoming
+    ray survives), Combines nested on both sides, and two scatterers (two hemisphere draws, A's ray kept)."""
+    d1, d2, em = diffuse((0.8, 0.7, 0.6)), diffuse((0.2, 0.4, 0.9)), emissive((0.3, 0.2, 0.1))
+    return [
+        ("sphere", (0.0, 0.2, 0.0), 1.4, combine(em, d1)),
+        ("plane", (0.0, 1.0, 0.0), (0.0, -1.5, 0.0), combine(combine(d1, em), combine(reflective((0.9, 0.8, 0.7)), checker((0.7, 0.9, 0.8), 0.4)))),
+        ("capsule", (-2.6, -0.6, 0.5), (-1.6, 1.2, -0.5), 0.5, combine(d1, d2)),
+    ]
+
+
 SCENES = {"tris": tris_scene, "room": room_scene, "default": lambda: default_scene(True), "default_nofuzz": lambda: default_scene(False),
-          "quirk": quirk_scene, "shapes": shapes_scene, "edges": edges_scene, "edges_negative": lambda: edges_scene(True)}
+          "quirk": quirk_scene, "shapes": shapes_scene, "edges": edges_scene, "edges_negative": lambda: edges_scene(True),
+          "matedge": matedge_scene}
 
 
 def scene_bounds(scene, mesh_bounds):
