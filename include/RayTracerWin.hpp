@@ -229,6 +229,33 @@ private:
     ColorBuffer(const ColorBuffer&); ColorBuffer& operator=(const ColorBuffer&);
     rtw_framebuffer* Fb; int Width, Height;
 };
+// First-hit feature buffers (rtw_features of rtwin.h; the reference has no counterpart, its UseBaseColor preview pass comes nearest): per pixel
+// geom = (sum normal.xyz, sum depth), albedo = (sum base colour, pass count), ids = (shape, triangle); filled by RayTracerScene::RenderFeatures,
+// accumulated until Clear().  The second constructor wraps device memory the caller owns (width * height * 16, * 16 and * 8 bytes).
+class FeatureBuffers {
+public:
+    FeatureBuffers(RtwDevice& dev, int width, int height) : F(nullptr), Width(width), Height(height) { RtwCheck(rtw_features_create(dev.Get(), width, height, &F)); }
+    FeatureBuffers(RtwDevice& dev, int width, int height, void* geomDev, void* albedoDev, void* idsDev) : F(nullptr), Width(width), Height(height)
+    {
+        RtwCheck(rtw_features_wrap(dev.Get(), width, height, geomDev, albedoDev, idsDev, &F));
+    }
+    ~FeatureBuffers() { rtw_features_destroy(F); }
+    rtw_features* Get() const { return F; }
+    int bitmapWidth() const { return Width; }
+    int bitmapHeight() const { return Height; }
+    void Clear() { RtwCheck(rtw_features_clear(F)); }
+    // geom and albedo: 4 floats per pixel (the pass count as a float in albedo's fourth), ids: 2 ints per pixel; waits for the device's stream
+    void Read(std::vector<float>& geom, std::vector<float>& albedo, std::vector<int32_t>& ids)
+    {
+        const size_t n = (size_t)Width * Height;
+        geom.resize(n * 4); albedo.resize(n * 4); ids.resize(n * 2);
+        RtwCheck(rtw_features_read(F, geom.data(), albedo.data(), ids.data()));
+    }
+    void DevicePointers(void** geomDev, void** albedoDev, void** idsDev) { RtwCheck(rtw_features_device_pointers(F, geomDev, albedoDev, idsDev)); }
+private:
+    FeatureBuffers(const FeatureBuffers&); FeatureBuffers& operator=(const FeatureBuffers&);
+    rtw_features* F; int Width, Height;
+};
 
 // ---- Src/RayTracerScene.h --------------------------------------------------------------------------------------------------------
 class RayTracerScene {
@@ -298,6 +325,14 @@ public:
         RtwCheck(rtw_scene_set_lens(Scene, &lens));
     }
     rtw_lens GetLens() const { rtw_lens lens; RtwCheck(rtw_scene_get_lens(Scene, &lens)); return lens; }
+    // First-hit features (depth, shading normal, base colour, ids) of the passes FirstPass .. FirstPass + Passes - 1 over this rank's tasks, accumulated
+    // into Buffers: the camera rays a render of the same passes builds, under the current camera and lens.  Asynchronous: rtw_render_features
+    void RenderFeatures(FeatureBuffers& Buffers, int FirstPass = 0, int Passes = 1, int SubSamples = 4, uint32_t Seed = 12345,
+                        int TaskRows = 10, int Rank = 0, int World = 1)
+    {
+        Commit();
+        RtwCheck(rtw_render_features(Scene, Buffers.Get(), TaskRows, Rank, World, FirstPass, Passes, SubSamples, Seed));
+    }
     void Commit() { if (!Committed) { RtwCheck(rtw_scene_commit(Scene)); Committed = true; } }
     rtw_scene* Get() { Commit(); return Scene; }
 private:

@@ -304,6 +304,41 @@ int rtw_render_passes(rtw_scene* scene, rtw_framebuffer* fb, int task_rows, int 
  * context's streams -- measured 0.3 ms inside a timed call).  UpdateBitmapPixels has no counterpart: its buffers are static arrays. */
 int rtw_render_reserve(rtw_scene* scene, rtw_framebuffer* fb, int task_rows, int rank, int world,
                        int max_bounce, int n_passes, int sub_samples);
+/* ---- first-hit feature buffers: depth, normal, albedo and ids per pixel (what a denoiser, a compositor or a picking tool asks for first) ----
+ * No reference counterpart (the nearest thing is its UseBaseColor preview pass).  Take pixel p, pass k and sub-sample i: the SAMPLE RAY is exactly the
+ * camera ray the render kernels build for (p, k, i, seed) under the scene's current camera and lens -- rtw_lens_rays' ray bit for bit.
+ * FindIntersectionWithScene of that ray gives the sample's values:
+ *     depth            Result.Distance (along the ray from its origin, not a z-depth);                    a miss: the ray's own distance, 1000.0f
+ *     normal           Result.HitNormal (the world-space shading normal rtw_trace_closest reports);       a miss: (0, 0, 0)
+ *     albedo           RayTrace(ray, 1, RenderOption{UseBaseColor = true}) = PreviewColor(Result) * Result.SampledColor, the shared-RayHitResult colour
+ *                      inheritance included; a texel's alpha plays no part;                               a miss: the sky colour
+ *     shape, triangle  what rtw_trace_closest reports for the ray;                                        a miss: -1, -1
+ * Per pass and pixel each of the seven float channels takes c = (v_0 + v_1 + ... + v_{ns-1}) / ns -- summed left to right in float32 from +0, no division
+ * when ns == 1 (the shape of ThreadWorker_Render's pass colour); per call, for the passes in order: sum += c, count += 1 (AccumulatePixel::AddPixel).
+ * The ids are those of sub-sample 0 of the LAST pass of the call.  Three buffers, 40 bytes per pixel:
+ *     geom    float4   (sum normal.xyz, sum depth)
+ *     albedo  float4   (sum albedo.rgb, int count in the bits of w, like the accumulator)
+ *     ids     int32 x 2 (shape, triangle)
+ * A call touches only the pixels of this rank's tasks (dealt as rtw_render_passes deals them); calls accumulate until rtw_features_clear.  The result
+ * depends on the scene, camera, lens, frame shape, sub_samples, passes and seed only -- never on an option of the context or the scene. */
+typedef struct rtw_features rtw_features;
+int rtw_features_create(rtw_context* ctx, int width, int height, rtw_features** out);
+/* wrap caller-owned device memory (e.g. torch tensors): geom and albedo width*height*16 bytes, 16-byte aligned; ids width*height*8 bytes, 8-byte aligned */
+int rtw_features_wrap(rtw_context* ctx, int width, int height, void* geom_dev, void* albedo_dev, void* ids_dev, rtw_features** out);
+int rtw_features_destroy(rtw_features* f);
+/* all sums and counts to zero, ids to (-1, -1); asynchronous on the context's stream */
+int rtw_features_clear(rtw_features* f);
+/* copy out (any pointer may be NULL): geom4 / albedo4 = width*height*4 floats, the count returned as a float like rtw_framebuffer_read_float; ids2 = width*height*2 */
+int rtw_features_read(rtw_features* f, float* geom4, float* albedo4, int32_t* ids2);
+int rtw_features_device_pointers(rtw_features* f, void** geom_dev, void** albedo_dev, void** ids_dev);
+/* Passes first_pass .. first_pass + n_passes - 1 of this rank's tasks into f.  Asynchronous on the context's stream: one or two launches, and no allocation,
+ * copy or synchronisation once the frame shape's screen bins and tile tables exist (the cached tables of rtw_render_passes, built the same way when they are
+ * missing).  RTW_ERR_STATE for an uncommitted scene; RTW_ERR_INVALID for bad sizes, counts or handles or a features object of another context;
+ * RTW_ERR_LIMIT for a pass index >= 2^29 with a lens.  rtw_scene_set_camera / rtw_scene_set_lens between calls behave as for rendering.  The work
+ * counters (rtw_stats) are not touched. */
+int rtw_render_features(rtw_scene* scene, rtw_features* f, int task_rows, int rank, int world,
+                        int first_pass, int n_passes, int sub_samples, uint32_t seed);
+
 /* Device memory the context holds: workspaces + its share of the 201 MB unit-vector table (one copy per device, shared by the contexts on it).
  * The workspace is sized by the largest group of passes rendered (or reserved) so far: per path slot 116 B + 48 B x max_bounce, slots = pixels of the
  * frame's busy tiles x sub-samples x passes per group; e.g. TorusKnot 1080p depth 4: 21 MB for one pass per call,

@@ -415,6 +415,75 @@ class Framebuffer:
             pass
 
 
+class FeatureBuffers:
+    """First-hit feature buffers (rtw_features of include/rtwin.h): per pixel the sums of shading normal and depth (geom), of the base
+    colour plus the pass count (albedo) and the ids (shape, triangle) of what the pixel's camera rays meet first; filled by
+    RayTracerScene.render_features, accumulated until clear()."""
+
+    def __init__(self, ctx, width, height, _wrap=None):
+        self.ctx, self.width, self.height = ctx, int(width), int(height)
+        self.h = C.c_void_p()
+        self._tensors = _wrap       # wrapped torch tensors stay alive with the object
+        ctx._children.add(self)
+        if _wrap is None:
+            _check(library().rtw_features_create(ctx.h, self.width, self.height, C.byref(self.h)))
+        else:
+            _check(library().rtw_features_wrap(ctx.h, self.width, self.height, *[C.c_void_p(t.data_ptr()) for t in _wrap], C.byref(self.h)))
+
+    @classmethod
+    def wrap(cls, ctx, geom, albedo, ids):
+        """Over torch tensors on the context's device, contiguous: geom and albedo float32 (H, W, 4), ids int32 (H, W, 2).  The kernels write
+        straight into them (asynchronously on the context's stream); albedo[..., 3] holds the pass count as int32 bits (view it as int32)."""
+        import torch
+        if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() for t in (geom, albedo, ids)):
+            raise ValueError("FeatureBuffers.wrap: geom, albedo and ids must be contiguous torch tensors on the context's device")
+        if geom.dtype != torch.float32 or albedo.dtype != torch.float32 or ids.dtype != torch.int32:
+            raise ValueError("FeatureBuffers.wrap: geom and albedo must be float32, ids int32")
+        if geom.dim() != 3 or geom.shape[2] != 4 or tuple(albedo.shape) != tuple(geom.shape) or tuple(ids.shape) != (geom.shape[0], geom.shape[1], 2):
+            raise ValueError("FeatureBuffers.wrap: shapes must be (H, W, 4), (H, W, 4) and (H, W, 2)")
+        if any(t.device.index != ctx.device for t in (geom, albedo, ids)):
+            raise ValueError("FeatureBuffers.wrap: the tensors must live on the context's device %d" % ctx.device)
+        return cls(ctx, geom.shape[1], geom.shape[0], _wrap=(geom, albedo, ids))
+
+    def clear(self):
+        _check(library().rtw_features_clear(self.h))
+
+    def read(self):
+        """(geom (n, 4) float32 = sum normal.xyz, sum depth; albedo (n, 4) float32 = sum albedo.rgb, pass count as a float; ids (n, 2) int32 =
+        shape, triangle) for the n = width * height pixels; waits for the context's stream"""
+        n = self.width * self.height
+        geom, albedo, ids = np.empty((n, 4), np.float32), np.empty((n, 4), np.float32), np.empty((n, 2), np.int32)
+        _check(library().rtw_features_read(self.h, _p(geom), _p(albedo), _p(ids)))
+        return geom, albedo, ids
+
+    def means(self):
+        """(depth (n,), normal (n, 3), albedo (n, 3)): the sums divided by the pass count in float32 on the host -- no division at count 1, and
+        pixels no pass has reached (count 0) keep their zeros"""
+        geom, albedo, _ = self.read()
+        count = albedo[:, 3]
+        div = np.where(count > 1, count, np.float32(1.0)).astype(np.float32)
+        depth = np.where(count > 1, geom[:, 3] / div, geom[:, 3]).astype(np.float32)
+        normal = np.where(count[:, None] > 1, geom[:, :3] / div[:, None], geom[:, :3]).astype(np.float32)
+        color = np.where(count[:, None] > 1, albedo[:, :3] / div[:, None], albedo[:, :3]).astype(np.float32)
+        return depth, normal, color
+
+    def device_pointers(self):
+        g, a, i = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(library().rtw_features_device_pointers(self.h, C.byref(g), C.byref(a), C.byref(i)))
+        return g.value, a.value, i.value
+
+    def close(self):
+        if getattr(self, "h", None):
+            library().rtw_features_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Camera(C.Structure):
     """rtw_camera: a ray looks from `eye` along (right * (dx + ox) + up * (dy + oy)) + forward * focal, normalized."""
     _fields_ = [("eye", C.c_float * 3), ("right", C.c_float * 3), ("up", C.c_float * 3), ("forward", C.c_float * 3), ("focal", C.c_float)]
@@ -718,6 +787,13 @@ class RayTracerScene:
         _check(library().rtw_render_passes(self.h, fb.h, int(task_rows), int(rank), int(world), int(MaxBounceCount),
                                            int(opt.UseBaseColor), int(first_pass), int(n_passes), int(sub_samples),
                                            C.c_uint32(seed)))
+
+    def render_features(self, fb, task_rows=10, rank=0, world=1, first_pass=0, n_passes=1, sub_samples=4, seed=12345):
+        """rtw_render_features: the first-hit features of the passes first_pass .. first_pass + n_passes - 1 over this rank's tasks, accumulated
+        into the FeatureBuffers fb -- the camera rays render_passes builds for the same arguments.  Asynchronous on the context's stream."""
+        self.commit()
+        _check(library().rtw_render_features(self.h, fb.h, int(task_rows), int(rank), int(world), int(first_pass), int(n_passes),
+                                             int(sub_samples), C.c_uint32(seed)))
 
     def render_reserve(self, fb, task_rows, rank, world, MaxBounceCount, n_passes, sub_samples=4):
         """rtw_render_reserve: bins, tile tables and workspace of a later render_passes call with these arguments (renders nothing)"""

@@ -74,6 +74,14 @@ struct GroupTuning : AuxFork {      // (the sky-only tiles run on aux_stream bes
     hipEvent_t* timing = nullptr;  // null, or 4 events: before the primary kernel, after it, after the bounce rounds, after resolve
 };
 int launch_render_group(const RtwSceneDev* sc, void* accum, void* argb, void* workspace, const RtwGroupParams& g, const GroupTuning& tune, bool stats, hipStream_t stream);
+// ---- first-hit feature buffers (rtw_feature_kernels.h): g holds the frame, the tile mapping and the busy / sky tile lists of a group launch (rp.preview and
+// rp.max_bounce are not read); geom / albedo: float4 per pixel, ids: int32 x 2 per pixel ----
+struct FeatureTuning {
+    int cu_count = 256, sky_blocks = 4;
+    bool has_analytic = false;     // some shape is a sphere / plane / capsule / triangle
+    bool carry = false;            // ... and one of them follows a textured mesh: its hits can keep that mesh hit's sampled colour
+};
+int launch_render_features(const RtwSceneDev* sc, void* geom, void* albedo, void* ids, const RtwGroupParams& g, const FeatureTuning& tune, hipStream_t stream);
 // ---- KdNode::Build and the layouts derived from the tree, on the device (rtw_build_kernels.h) ----
 struct DeviceBuildIn {      // the arrays RMeshShape owns (host memory)
     const float* points; int n_points; const float* texcoords; int n_texcoords; const float* normals; int n_normals;

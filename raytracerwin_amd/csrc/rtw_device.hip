@@ -1102,6 +1102,7 @@ __global__ __launch_bounds__(256, 3) void shade_kernel(const RtwSceneDev* __rest
 
 #include "rtw_wave_kernels.h"
 #include "rtw_group_kernels.h"
+#include "rtw_feature_kernels.h"
 #include "rtw_query_kernels.h"
 #include "rtw_build_kernels.h"
 
@@ -1542,6 +1543,28 @@ int launch_render_group(const RtwSceneDev* sc, void* accum, void* argb, void* wo
     }
     join_sky(tune, forked, stream);
     if (tune.timing) (void)hipEventRecord(tune.timing[3], stream);
+    return (int)hipGetLastError();
+}
+
+// ---- first-hit feature buffers (rtw_feature_kernels.h): the sky-only tiles, then a wave per busy tile; no workspace, nothing but the two launches ----
+int launch_render_features(const RtwSceneDev* sc, void* geom, void* albedo, void* ids, const RtwGroupParams& g, const FeatureTuning& tune, hipStream_t stream)
+{
+    const RtwRenderParams& p = g.rp;
+    if (g.n_passes <= 0 || (g.n_busy <= 0 && g.n_sky <= 0)) return 0;
+    FeatureBufs fb;
+    fb.geom = (float4*)geom; fb.albedo = (float4*)albedo; fb.ids = (unsigned long long*)ids;
+    if (g.n_sky > 0) {
+        int sgrid = (g.n_sky + 3) / 4;
+        if (sgrid > tune.cu_count * tune.sky_blocks) sgrid = tune.cu_count * tune.sky_blocks;
+        with_flags(p.cam_general != 0, [&](auto CAM) { launch(gfeature_sky_kernel<decltype(CAM)::value>, dim3(sgrid), dim3(256), 0, stream, fb, g); });
+    }
+    if (g.n_busy > 0) {
+        const unsigned grid = (unsigned)((g.n_busy + 3) / 4);
+        with_flags(tune.has_analytic, p.cam_general != 0, p.lens != 0, [&](auto AN, auto CAM, auto LENS) {
+            constexpr bool lens = decltype(LENS)::value, cam = decltype(CAM)::value || lens;
+            launch(gfeature_kernel<decltype(AN)::value, cam, lens>, dim3(grid), dim3(256), 0, stream, sc, fb, g, tune.carry ? 1 : 0);
+        });
+    }
     return (int)hipGetLastError();
 }
 

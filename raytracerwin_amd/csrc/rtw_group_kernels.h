@@ -431,6 +431,7 @@ __global__ __launch_bounds__(256, RTW_GPRIMARY_MINB) void gprimary_kernel(const 
                 }
             } else if (p.max_bounce != 0) {                      // RayTrace(.., 0) is black (Src/RayTracerScene.cpp:39)
                 // FindIntersectionWithScene of the camera ray (Src/RayTracerScene.cpp:99-125), shapes in insertion order
+                // (rtw_feature_kernels.h feature_find is a COPY of this per-shape loop without the counters: a fix here is a fix there too)
                 int hit_shape = -1, hit_slot = -1, carry_shape = -1, carry_slot = -1;
                 f3 hit_pos = mk(0, 0, 0), carry_pos = mk(0, 0, 0);
                 float seg = ray.dist, carry_dist = 0.0f;

@@ -206,6 +206,15 @@ struct rtw_framebuffer {
     bool owned = false;
 };
 
+struct rtw_features {       // first-hit feature buffers: geom / albedo float4 per pixel, ids int32 x 2 per pixel
+    rtw_context* ctx = nullptr;
+    int width = 0, height = 0;
+    void* geom = nullptr;
+    void* albedo = nullptr;
+    void* ids = nullptr;
+    bool owned = false;
+};
+
 namespace {
 template <typename T>
 int upload(rtw_scene* scene, const std::vector<T>& v, const T** out)
@@ -1965,6 +1974,130 @@ int rtw_render_reserve(rtw_scene* scene, rtw_framebuffer* fb, int task_rows, int
     return rc;
 }
 
+
+// ---- first-hit feature buffers (rtw_feature_kernels.h) ---------------------------------------------------------------------------
+int rtw_features_create(rtw_context* ctx, int width, int height, rtw_features** out)
+{
+    if (!ctx || !out || width <= 0 || height <= 0) return fail(RTW_ERR_INVALID, "bad argument");
+    if ((int64_t)width * height > (int64_t)1 << 30) return fail(RTW_ERR_LIMIT, "feature buffers too large");
+    HIP_TRY(hipSetDevice(ctx->device));
+    std::unique_ptr<rtw_features> f(new rtw_features());
+    f->ctx = ctx; f->width = width; f->height = height; f->owned = true;
+    const size_t n = (size_t)width * (size_t)height;
+    hipError_t e = hipMalloc(&f->geom, n * 16);
+    if (e == hipSuccess) e = hipMalloc(&f->albedo, n * 16);
+    if (e == hipSuccess) e = hipMalloc(&f->ids, n * 8);
+    if (e != hipSuccess) {
+        (void)hipFree(f->geom); (void)hipFree(f->albedo); (void)hipFree(f->ids);
+        return hip_fail(e, "hipMalloc of the feature buffers");
+    }
+    const int rc = rtw_features_clear(f.get());
+    if (rc != RTW_OK) { (void)hipFree(f->geom); (void)hipFree(f->albedo); (void)hipFree(f->ids); return rc; }
+    *out = f.release();
+    return RTW_OK;
+}
+
+int rtw_features_wrap(rtw_context* ctx, int width, int height, void* geom_dev, void* albedo_dev, void* ids_dev, rtw_features** out)
+{
+    if (!ctx || !out || width <= 0 || height <= 0 || !geom_dev || !albedo_dev || !ids_dev) return fail(RTW_ERR_INVALID, "bad argument");
+    if ((int64_t)width * height > (int64_t)1 << 30) return fail(RTW_ERR_LIMIT, "feature buffers too large");
+    if (((uintptr_t)geom_dev & 15u) || ((uintptr_t)albedo_dev & 15u) || ((uintptr_t)ids_dev & 7u))
+        return fail(RTW_ERR_INVALID, "geom and albedo must be 16-byte aligned, ids 8-byte aligned");
+    rtw_features* f = new rtw_features();
+    f->ctx = ctx; f->width = width; f->height = height; f->owned = false;
+    f->geom = geom_dev; f->albedo = albedo_dev; f->ids = ids_dev;
+    *out = f;
+    return RTW_OK;
+}
+
+int rtw_features_destroy(rtw_features* f)
+{
+    if (!f) return RTW_OK;
+    if (f->owned) {
+        (void)hipSetDevice(f->ctx->device);
+        (void)hipStreamSynchronize(f->ctx->stream);
+        (void)hipFree(f->geom); (void)hipFree(f->albedo); (void)hipFree(f->ids);
+    }
+    delete f;
+    return RTW_OK;
+}
+
+int rtw_features_clear(rtw_features* f)
+{
+    if (!f) return fail(RTW_ERR_INVALID, "features object is null");
+    HIP_TRY(hipSetDevice(f->ctx->device));
+    const size_t n = (size_t)f->width * (size_t)f->height;
+    HIP_TRY(hipMemsetAsync(f->geom, 0, n * 16, f->ctx->stream));
+    HIP_TRY(hipMemsetAsync(f->albedo, 0, n * 16, f->ctx->stream));
+    HIP_TRY(hipMemsetAsync(f->ids, 0xFF, n * 8, f->ctx->stream));       // (-1, -1): nothing seen yet
+    return RTW_OK;
+}
+
+int rtw_features_read(rtw_features* f, float* geom4, float* albedo4, int32_t* ids2)
+{
+    if (!f) return fail(RTW_ERR_INVALID, "features object is null");
+    HIP_TRY(hipSetDevice(f->ctx->device));
+    const size_t n = (size_t)f->width * (size_t)f->height;
+    hipStream_t st = f->ctx->stream;
+    if (geom4) HIP_TRY(hipMemcpyAsync(geom4, f->geom, n * 16, hipMemcpyDeviceToHost, st));
+    if (albedo4) HIP_TRY(hipMemcpyAsync(albedo4, f->albedo, n * 16, hipMemcpyDeviceToHost, st));
+    if (ids2) HIP_TRY(hipMemcpyAsync(ids2, f->ids, n * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (albedo4) for (size_t i = 0; i < n; i++) {       // the count travels as int bits on the device
+        int32_t c; std::memcpy(&c, &albedo4[i * 4 + 3], 4);
+        albedo4[i * 4 + 3] = (float)c;
+    }
+    return RTW_OK;
+}
+
+int rtw_features_device_pointers(rtw_features* f, void** geom_dev, void** albedo_dev, void** ids_dev)
+{
+    if (!f) return fail(RTW_ERR_INVALID, "features object is null");
+    if (geom_dev) *geom_dev = f->geom;
+    if (albedo_dev) *albedo_dev = f->albedo;
+    if (ids_dev) *ids_dev = f->ids;
+    return RTW_OK;
+}
+
+// The call's passes over this rank's tasks: the sky-only tiles and the busy tiles of the group tables rtw_render_passes uses (built here the same way when
+// this frame shape has not been rendered yet), one launch each.  Whatever the context's pipeline, the scene's traversal or the work counters say: they
+// steer how an image is rendered, the feature kernels take none of those routes.
+int rtw_render_features(rtw_scene* scene, rtw_features* f, int task_rows, int rank, int world, int first_pass, int n_passes, int sub_samples, uint32_t seed)
+{
+    int rc = need_committed(scene); if (rc != RTW_OK) return rc;
+    if (!f) return fail(RTW_ERR_INVALID, "features object is null");
+    if (f->ctx != scene->ctx) return fail(RTW_ERR_INVALID, "scene and features object belong to different contexts");
+    if (n_passes < 0 || first_pass < 0) return fail(RTW_ERR_INVALID, "bad pass range");
+    if (sub_samples < 1 || sub_samples > 4) return fail(RTW_ERR_INVALID, "sub_samples must be 1..4");
+    if (scene->has_lens() && (long long)first_pass + n_passes > (1ll << 29)) return fail(RTW_ERR_LIMIT, "pass_index must stay below 2^29 with a lens");
+    rtw_context* cx = scene->ctx;
+    rtw_framebuffer frame; frame.ctx = cx; frame.width = f->width; frame.height = f->height;       // (the frame's shape, for rank_share)
+    RtwRenderParams p;
+    rc = rank_share(&frame, task_rows, rank, world, &p); if (rc != RTW_OK) return rc;
+    if (p.count == 0 || n_passes == 0) return RTW_OK;
+    p.width = f->width; p.height = f->height;
+    p.max_bounce = 1; p.preview = 1; p.pass_index = first_pass; p.sub_samples = sub_samples; p.seed = seed;
+    set_camera_params(scene, p);
+    const int last_pixel = f->width * f->height - 1;
+    if (!choose_group_tiles(p, 0, last_pixel)) return fail(RTW_ERR_LIMIT, "frame too large for the tile mapping");
+    rtw_scene::BinSet* bs = nullptr;
+    rc = scene_bins(scene, p.width, p.height, p.tile_w, p.tile_h, &bs); if (rc != RTW_OK) return rc;
+    p.bins = bs->d_bins; p.cam_dx = bs->d_dx; p.cam_dy = bs->d_dy;
+    const rtw_scene::GroupTable* gt = nullptr;
+    rc = scene_group_table(scene, *bs, p, sub_samples, &gt); if (rc != RTW_OK) return rc;
+    RtwGroupParams g; std::memset(&g, 0, sizeof g);
+    g.rp = p;
+    g.first_pass = first_pass; g.n_passes = n_passes;
+    g.range_begin = 0; g.range_end = last_pixel; g.first_tile = 0;
+    g.n_busy = gt->n_busy; g.n_sky = gt->n_sky; g.n_jobs = gt->n_busy;      // a wave per busy TILE: the per-sub-sample jobs are the primary kernel's
+    g.busy_tiles = gt->d_busy; g.sky_tiles = gt->d_sky; g.jobs = nullptr;
+    rtw::FeatureTuning tune;
+    tune.cu_count = cx->cu_count; tune.sky_blocks = cx->sky_blocks;
+    tune.has_analytic = scene->has_analytic; tune.carry = scene->texture_carry;
+    const hipError_t e = (hipError_t)rtw::launch_render_features(scene->d_scene, f->geom, f->albedo, f->ids, g, tune, cx->stream);
+    if (e != hipSuccess) return hip_fail(e, "feature launch");
+    return RTW_OK;
+}
 
 // device memory this context holds right now: the group workspaces, the older pipelines' workspace and its share of the unit-vector table
 // (201 MB per device, shared by the contexts on it); scenes and framebuffers are the caller's objects and not counted
