@@ -256,6 +256,13 @@ private:
     FeatureBuffers(const FeatureBuffers&); FeatureBuffers& operator=(const FeatureBuffers&);
     rtw_features* F; int Width, Height;
 };
+// rtw_denoise: the edge-avoiding a-trous filter of Source guided by Features into Destination (another buffer of the same size), after which
+// Destination is an ordinary one-pass ColorBuffer (bitcolor(), accuBuffer()).  Asynchronous; the formula and the parameters are rtwin.h's.
+inline rtw_denoise_params DenoiseDefaults() { rtw_denoise_params p; RtwCheck(rtw_denoise_default_params(&p)); return p; }
+inline void Denoise(ColorBuffer& Source, FeatureBuffers& Features, ColorBuffer& Destination, const rtw_denoise_params& Params = DenoiseDefaults())
+{
+    RtwCheck(rtw_denoise(Source.Get(), Features.Get(), &Params, Destination.Get()));
+}
 
 // ---- Src/RayTracerScene.h --------------------------------------------------------------------------------------------------------
 class RayTracerScene {

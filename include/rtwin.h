@@ -99,6 +99,7 @@ int rtw_context_synchronize(rtw_context* ctx);
  *   "workspace_limit_mb" (0 = 24 GiB) a group's workspace may not exceed this: larger groups are re-formed smaller (see rtw_context_memory_bytes);
  *   "device_build" (1) tree, layouts and screen bins built on the device; "hint_period" (16) pipeline 3: the queue lengths that size the next launches
  *                   are read back every n-th pass; "kernel_timing" 1 = record events around the stages of each pass / group (rtw_last_pass_kernel_ms);
+ *   "denoise_tiling" (-1) which tiling each level of rtw_denoise runs: 0 = dense, 1 = lattice, -1 = the measured rule; the result is the same bits;
  *   "query_kernel"  (-1) which kernel the device queries (rtw_trace_closest_device / rtw_trace_occluded_device / rtw_trace_occluded) run: 1 = the ray-per-lane
  *                   query kernel (rtw_query_kernels.h); 0 = the kernel of rtw_trace_closest on the caller's buffers (any-hit: a closest query whose
  *                   shape >= 0 becomes the byte) -- the A/B baseline and cross-check; -1 = the measured rule (profiles/query_experiments.md): any-hit on
@@ -338,6 +339,44 @@ int rtw_features_device_pointers(rtw_features* f, void** geom_dev, void** albedo
  * counters (rtw_stats) are not touched. */
 int rtw_render_features(rtw_scene* scene, rtw_features* f, int task_rows, int rank, int world,
                         int first_pass, int n_passes, int sub_samples, uint32_t seed);
+
+/* ---- edge-avoiding a-trous denoiser over a framebuffer and its feature buffers (Dammertz et al. 2010; no reference counterpart) ----
+ * An image-space filter guided by the first-hit features, with the base colour divided out first so that textures stay sharp.  It takes buffers and no
+ * scene, so it serves any image the caller can describe this way.  src: accum = (sum.xyz, int count_fb); f: geom = (sum normal.xyz, sum depth), albedo =
+ * (sum rgb, int count_f), ids = (shape, triangle); dst: another framebuffer.  Same width and height, same context, dst != src.  Per pixel
+ *     C = accum.xyz / count_fb      n = geom.xyz / count_f (not renormalised)      z = geom.w / count_f      A = albedo.rgb / count_f      s = shape id
+ * A pixel is EMPTY when either count is 0 and BAD when a channel of C is not finite.  EPS = 1e-3f.
+ * I_0 = C / (A + EPS) per channel with RTW_DENOISE_DEMODULATE, else I_0 = C.  For level i = 0 .. levels-1, step = 2^i, for every non-empty pixel p:
+ *     sw = 0, sc = 0
+ *     for dy = -2..2, for dx = -2..2            (in this order)
+ *         q = p + step * (dx, dy)
+ *         skip q when it is outside the frame, empty or bad
+ *         skip q when RTW_DENOISE_SAME_SHAPE is set and s_q != s_p
+ *         e = 0
+ *         if sigma_color  > 0 and p is not bad:  e += |I_i(p) - I_i(q)|^2 / (sigma_color * 2^-i)^2
+ *         if sigma_normal > 0:                   e += |n_p - n_q|^2 / sigma_normal^2
+ *         if sigma_depth  > 0:                   e += ((z_p - z_q) / (sigma_depth * max(|z_p|, 1e-6)))^2
+ *         w = h[dx] * h[dy] * exp(-e)            h = (1/16, 1/4, 3/8, 1/4, 1/16)
+ *         sw += w;  sc += w * I_i(q)
+ *     I_{i+1}(p) = sc / sw   when sw > 0
+ *                  I_i(p)    when sw == 0 and p is not bad
+ *                  0         otherwise
+ * out = I_levels * (A + EPS) with RTW_DENOISE_DEMODULATE, else I_levels; an empty pixel gives (0, 0, 0).  dst.accum takes (out.xyz, count 1), dst.argb
+ * the gamma pack of out (the thresholds of rtw_gamma_thresholds): dst is then an ordinary one-pass framebuffer for every other call.  src and f are not
+ * written.  A non-positive sigma switches its term off.  Misses (depth 1000, normal 0, id -1) are their own "surface".  Everything is float32, the taps
+ * are summed in the stated order, exp(-e) is the hardware exp2 of -e * log2(e); shape ids are compared in their low 30 bits.
+ * Asynchronous on the context's stream: 1 + levels launches.  The work space (two float4 images and a 20-byte guide record per pixel, 52 bytes per
+ * pixel) belongs to the context, grows only, is counted by rtw_context_memory_bytes and released by rtw_context_trim: a repeated call of the same size
+ * does no allocation, copy or synchronisation.  The context option "denoise_tiling" (-1) picks each level's tiling -- 0 = dense tiles with a halo,
+ * 1 = tiles of the step's lattices, -1 = the faster by measurement -- and never changes a result: both give the same bits.
+ * RTW_ERR_INVALID: a null handle, differing sizes, handles of different contexts, dst == src, levels outside 1..6, a NaN sigma, unknown flag bits. */
+#define RTW_DENOISE_DEMODULATE 1u
+#define RTW_DENOISE_SAME_SHAPE 2u
+typedef struct rtw_denoise_params { int levels; float sigma_color, sigma_normal, sigma_depth; uint32_t flags; } rtw_denoise_params;
+/* 5 levels, both flags, sigma_color 0.6 (on the demodulated colour, i.e. in units of the surface's own brightness; halved per level as the paper does),
+ * sigma_normal 0.3 (|n_p - n_q| of about 17 degrees costs a factor e), sigma_depth 0.1 (a relative distance step of 10 % costs a factor e) */
+int rtw_denoise_default_params(rtw_denoise_params* p);
+int rtw_denoise(rtw_framebuffer* src, rtw_features* f, const rtw_denoise_params* p, rtw_framebuffer* dst);
 
 /* Device memory the context holds: workspaces + its share of the 201 MB unit-vector table (one copy per device, shared by the contexts on it).
  * The workspace is sized by the largest group of passes rendered (or reserved) so far: per path slot 116 B + 48 B x max_bounce, slots = pixels of the

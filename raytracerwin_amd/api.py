@@ -484,6 +484,26 @@ class FeatureBuffers:
             pass
 
 
+class DenoiseParams(C.Structure):
+    """rtw_denoise_params; DenoiseParams() holds rtw_denoise_default_params' values (5 levels, both flags), keywords override them"""
+    _fields_ = [("levels", C.c_int), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("flags", C.c_uint32)]
+    DEMODULATE, SAME_SHAPE = 1, 2
+
+    def __init__(self, **kw):
+        super().__init__()
+        _check(library().rtw_denoise_default_params(C.byref(self)))
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+def denoise(src, features, dst, params=None):
+    """rtw_denoise: the edge-avoiding a-trous filter (the formula is include/rtwin.h's) of the Framebuffer src, guided by the FeatureBuffers, into
+    the Framebuffer dst -- afterwards an ordinary one-pass framebuffer (read_float, resolve_argb, save_png).  Created or wrapped buffers alike;
+    asynchronous on the context's stream."""
+    params = params if params is not None else DenoiseParams()
+    _check(library().rtw_denoise(src.h, features.h, C.byref(params), dst.h))
+
+
 class Camera(C.Structure):
     """rtw_camera: a ray looks from `eye` along (right * (dx + ox) + up * (dy + oy)) + forward * focal, normalized."""
     _fields_ = [("eye", C.c_float * 3), ("right", C.c_float * 3), ("up", C.c_float * 3), ("forward", C.c_float * 3), ("focal", C.c_float)]

@@ -82,6 +82,22 @@ struct FeatureTuning {
     bool carry = false;            // ... and one of them follows a textured mesh: its hits can keep that mesh hit's sampled colour
 };
 int launch_render_features(const RtwSceneDev* sc, void* geom, void* albedo, void* ids, const RtwGroupParams& g, const FeatureTuning& tune, hipStream_t stream);
+// ---- the a-trous denoiser over a framebuffer and its feature buffers (rtw_denoise_kernels.h): prepare, then `levels` level launches ping-ponging
+// between the workspace's two images, the last one writing dst.  Nothing but launches on `stream`. ----
+constexpr uint32_t DENOISE_DEMODULATE = 1u, DENOISE_SAME_SHAPE = 2u;      // == RTW_DENOISE_* of rtwin.h
+struct DenoiseCall {
+    const void *accum, *geom, *albedo, *ids;    // the sources (never written)
+    void* workspace;                            // denoise_workspace_bytes(width, height)
+    void *dst_accum, *dst_argb;
+    const float* gamma_thr;
+    int width, height, levels;
+    float sigma_color, sigma_normal, sigma_depth;
+    uint32_t flags;
+    int tiling;                                 // per level: 0 = dense, 1 = lattice, -1 = the measured rule (denoise_level_is_lattice)
+};
+size_t denoise_workspace_bytes(int width, int height);     // two float4 images + the guide records (16 + 4 bytes): 52 bytes per pixel
+bool denoise_level_is_lattice(int tiling, int step);
+int launch_denoise(const DenoiseCall& d, hipStream_t stream);
 // ---- KdNode::Build and the layouts derived from the tree, on the device (rtw_build_kernels.h) ----
 struct DeviceBuildIn {      // the arrays RMeshShape owns (host memory)
     const float* points; int n_points; const float* texcoords; int n_texcoords; const float* normals; int n_normals;

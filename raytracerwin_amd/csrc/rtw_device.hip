@@ -1103,6 +1103,7 @@ __global__ __launch_bounds__(256, 3) void shade_kernel(const RtwSceneDev* __rest
 #include "rtw_wave_kernels.h"
 #include "rtw_group_kernels.h"
 #include "rtw_feature_kernels.h"
+#include "rtw_denoise_kernels.h"
 #include "rtw_query_kernels.h"
 #include "rtw_build_kernels.h"
 
@@ -1564,6 +1565,62 @@ int launch_render_features(const RtwSceneDev* sc, void* geom, void* albedo, void
             constexpr bool lens = decltype(LENS)::value, cam = decltype(CAM)::value || lens;
             launch(gfeature_kernel<decltype(AN)::value, cam, lens>, dim3(grid), dim3(256), 0, stream, sc, fb, g, tune.carry ? 1 : 0);
         });
+    }
+    return (int)hipGetLastError();
+}
+
+// ---- the a-trous denoiser (rtw_denoise_kernels.h) ---------------------------------------------------------------------------------
+namespace {
+size_t dn_round(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+}  // namespace
+size_t denoise_workspace_bytes(int width, int height)
+{
+    const size_t n = (size_t)width * (size_t)height;
+    return 3 * dn_round(n * 16) + dn_round(n * 4);
+}
+// "denoise_tiling" -1, as measured with tools/denoise_bench.py at 1080p and 2160p (profiles/denoise_experiments.md section 2): from step 4 on the lattice
+// tiling is 1.6 to 2 x faster than the dense one (4.5 staged records per output against 2.5, then no reuse at all); at steps 1 and 2 the two are within
+// the session's spread, and dense (1.69 and 2.5 records per output, contiguous loads) stays.
+bool denoise_level_is_lattice(int tiling, int step) { return tiling < 0 ? step >= 4 : tiling != 0; }
+
+int launch_denoise(const DenoiseCall& d, hipStream_t stream)
+{
+    const size_t n = (size_t)d.width * (size_t)d.height, img = dn_round(n * 16);
+    char* ws = (char*)d.workspace;
+    float4* image[2] = { (float4*)ws, (float4*)(ws + img) };
+    DenoiseBufs b;
+    b.accum = (const float4*)d.accum; b.geom = (const float4*)d.geom; b.albedo = (const float4*)d.albedo; b.ids = (const unsigned long long*)d.ids;
+    b.guide = (float4*)(ws + 2 * img); b.key = (uint32_t*)(ws + 3 * img);
+    b.dst_accum = (float4*)d.dst_accum; b.dst_argb = (uint32_t*)d.dst_argb; b.gamma_thr = d.gamma_thr;
+    b.width = d.width; b.height = d.height; b.flags = d.flags;
+    launch(denoise_prepare_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, b, image[0]);
+    for (int i = 0; i < d.levels; i++) {
+        DenoiseLevel L;
+        L.in = image[i & 1]; L.out = image[(i + 1) & 1]; L.step = 1 << i;
+        const float sc = d.sigma_color / (float)(1 << i);
+        L.kc = d.sigma_color > 0.0f ? 1.0f / (sc * sc) : 0.0f;
+        L.kn = d.sigma_normal > 0.0f ? 1.0f / (d.sigma_normal * d.sigma_normal) : 0.0f;
+        L.kd = d.sigma_depth > 0.0f ? 1.0f / d.sigma_depth : 0.0f;
+        L.tiles_x = L.tiles_y = 0;
+        const bool last = i == d.levels - 1;
+        if (denoise_level_is_lattice(d.tiling, L.step)) {
+            const int rx = L.step < 4 ? L.step : 4, lw = (d.width + L.step - 1) / L.step, lh = (d.height + L.step - 1) / L.step;
+            L.tiles_x = (lw + 64 / rx - 1) / (64 / rx); L.tiles_y = (lh + DN_LAT_ROWS - 1) / DN_LAT_ROWS;
+            const dim3 grid((unsigned)(L.step / rx * L.tiles_x), (unsigned)(L.step * L.tiles_y));
+            const size_t lds = (size_t)(64 + 4 * rx) * (DN_LAT_ROWS + 4) * 36;
+            with_flags(last, [&](auto LAST) {
+                if (rx == 1) launch(denoise_level_kernel<DN_LATTICE, 1, decltype(LAST)::value>, grid, dim3(256), lds, stream, b, L);
+                else if (rx == 2) launch(denoise_level_kernel<DN_LATTICE, 2, decltype(LAST)::value>, grid, dim3(256), lds, stream, b, L);
+                else launch(denoise_level_kernel<DN_LATTICE, 4, decltype(LAST)::value>, grid, dim3(256), lds, stream, b, L);
+            });
+        } else {
+            const dim3 grid((unsigned)((d.width + DN_TILE_W - 1) / DN_TILE_W), (unsigned)((d.height + DN_TILE_H - 1) / DN_TILE_H));
+            const size_t lds = (size_t)(DN_TILE_W + 4 * L.step) * (DN_TILE_H + 4 * L.step) * 36;
+            with_flags(last, [&](auto LAST) {
+                if (L.step <= 4) launch(denoise_level_kernel<DN_DENSE, 1, decltype(LAST)::value>, grid, dim3(256), lds, stream, b, L);
+                else launch(denoise_level_kernel<DN_DIRECT, 1, decltype(LAST)::value>, grid, dim3(256), 0, stream, b, L);
+            });
+        }
     }
     return (int)hipGetLastError();
 }

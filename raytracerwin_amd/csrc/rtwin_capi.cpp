@@ -152,6 +152,10 @@ struct rtw_context {
     int lens_route = -1;                // option: pipeline 4 with a lens: 1 = the camera round (glens_kernel + the trace kernels), 0 = gprimary_kernel's LENS instantiation, -1 = the rule (lens_uses_camera_round)
     void* d_query_ws = nullptr;         // "query_kernel" 0 only: stand-ins for the outputs closest_kernel writes and the caller did not ask for (grown on demand)
     size_t query_ws_bytes = 0;
+    // rtw_denoise
+    int denoise_tiling = -1;            // option: each level's tiling: 0 = dense, 1 = lattice, -1 = the measured rule (rtw::denoise_level_is_lattice); same bits either way
+    void* d_denoise_ws = nullptr;       // two float4 images + the guide records of the largest frame denoised so far (grown on demand, rtw_context_trim frees it)
+    size_t denoise_ws_bytes = 0;
 };
 
 struct rtw_scene {
@@ -307,7 +311,7 @@ int rtw_context_destroy(rtw_context* ctx)
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     if (ctx->d_unit) release_device_table(ctx->device);
-    (void)hipFree(ctx->d_query_ws);
+    (void)hipFree(ctx->d_query_ws); (void)hipFree(ctx->d_denoise_ws);
     (void)hipFree(ctx->d_workspace); (void)hipFree(ctx->d_gamma); (void)hipFree(ctx->d_lut); (void)hipFree(ctx->d_stats);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
     if (ctx->aux_stream) { (void)hipStreamSynchronize(ctx->aux_stream); (void)hipStreamDestroy(ctx->aux_stream); }
@@ -365,6 +369,7 @@ int rtw_context_set_option(rtw_context* ctx, const char* name, int value)
         return RTW_OK;
     }
     if (std::strcmp(name, "query_kernel") == 0) { ctx->query_kernel = value < 0 ? -1 : (value ? 1 : 0); return RTW_OK; }
+    if (std::strcmp(name, "denoise_tiling") == 0) { ctx->denoise_tiling = value < 0 ? -1 : (value ? 1 : 0); return RTW_OK; }
     if (std::strcmp(name, "lens_route") == 0) { ctx->lens_route = value < 0 ? -1 : (value ? 1 : 0); return RTW_OK; }
     if (std::strcmp(name, "query_blocks") == 0) { ctx->query_blocks = value < 0 ? 0 : value; return RTW_OK; }
     if (std::strcmp(name, "hint_period") == 0) { ctx->hint_period = value < 1 ? 1 : value; return RTW_OK; }
@@ -2099,19 +2104,60 @@ int rtw_render_features(rtw_scene* scene, rtw_features* f, int task_rows, int ra
     return RTW_OK;
 }
 
+// ---- the a-trous denoiser (rtw_denoise_kernels.h; the formula is rtwin.h's) -------------------------------------------------------
+static_assert(RTW_DENOISE_DEMODULATE == rtw::DENOISE_DEMODULATE && RTW_DENOISE_SAME_SHAPE == rtw::DENOISE_SAME_SHAPE, "the kernels' flag bits are the header's");
+int rtw_denoise_default_params(rtw_denoise_params* p)
+{
+    if (!p) return fail(RTW_ERR_INVALID, "null");
+    p->levels = 5; p->sigma_color = 0.6f; p->sigma_normal = 0.3f; p->sigma_depth = 0.1f;
+    p->flags = RTW_DENOISE_DEMODULATE | RTW_DENOISE_SAME_SHAPE;
+    return RTW_OK;
+}
+
+int rtw_denoise(rtw_framebuffer* src, rtw_features* f, const rtw_denoise_params* p, rtw_framebuffer* dst)
+{
+    if (!src || !f || !p || !dst) return fail(RTW_ERR_INVALID, "null argument");
+    if (dst == src || dst->accum == src->accum || dst->argb == src->argb) return fail(RTW_ERR_INVALID, "the destination must not be the source");
+    if (src->ctx != f->ctx || src->ctx != dst->ctx) return fail(RTW_ERR_INVALID, "source, features and destination belong to different contexts");
+    if (src->width != f->width || src->height != f->height || src->width != dst->width || src->height != dst->height)
+        return fail(RTW_ERR_INVALID, "source, features and destination differ in size");
+    if (p->levels < 1 || p->levels > 6) return fail(RTW_ERR_INVALID, "levels must be 1..6");
+    if (std::isnan(p->sigma_color) || std::isnan(p->sigma_normal) || std::isnan(p->sigma_depth)) return fail(RTW_ERR_INVALID, "a sigma is NaN");
+    if (p->flags & ~(RTW_DENOISE_DEMODULATE | RTW_DENOISE_SAME_SHAPE)) return fail(RTW_ERR_INVALID, "unknown flag bits");
+    if ((int64_t)src->width * src->height > (int64_t)1 << 30) return fail(RTW_ERR_LIMIT, "frame too large");
+    rtw_context* cx = src->ctx;
+    HIP_TRY(hipSetDevice(cx->device));
+    const size_t need = rtw::denoise_workspace_bytes(src->width, src->height);
+    if (need > cx->denoise_ws_bytes) {      // grow only: an earlier call's launches may still read the old block
+        HIP_TRY(hipStreamSynchronize(cx->stream));
+        if (cx->d_denoise_ws) { (void)hipFree(cx->d_denoise_ws); cx->d_denoise_ws = nullptr; cx->denoise_ws_bytes = 0; }
+        HIP_TRY(hipMalloc(&cx->d_denoise_ws, need));
+        cx->denoise_ws_bytes = need;
+    }
+    rtw::DenoiseCall d;
+    d.accum = src->accum; d.geom = f->geom; d.albedo = f->albedo; d.ids = f->ids;
+    d.workspace = cx->d_denoise_ws; d.dst_accum = dst->accum; d.dst_argb = dst->argb; d.gamma_thr = cx->d_gamma;
+    d.width = src->width; d.height = src->height; d.levels = p->levels;
+    d.sigma_color = p->sigma_color; d.sigma_normal = p->sigma_normal; d.sigma_depth = p->sigma_depth;
+    d.flags = p->flags; d.tiling = cx->denoise_tiling;
+    const hipError_t e = (hipError_t)rtw::launch_denoise(d, cx->stream);
+    if (e != hipSuccess) return hip_fail(e, "denoise launch");
+    return RTW_OK;
+}
+
 // device memory this context holds right now: the group workspaces, the older pipelines' workspace and its share of the unit-vector table
 // (201 MB per device, shared by the contexts on it); scenes and framebuffers are the caller's objects and not counted
 long long rtw_context_memory_bytes(const rtw_context* ctx)
 {
     if (!ctx) return 0;
-    size_t g = 0; for (int j = 0; j < RTW_MAX_PARTS; j++) g += ctx->group_ws_bytes[j];
+    size_t g = ctx->denoise_ws_bytes; for (int j = 0; j < RTW_MAX_PARTS; j++) g += ctx->group_ws_bytes[j];
     return (long long)(g + ctx->workspace_bytes + (size_t)RTW_TABLE_SIZE * 3 * sizeof(float) + 2 * 1024 + 64);
 }
 // ... of which workspace (grows with the largest group rendered so far; rtw_context_trim gives it back)
 long long rtw_context_workspace_bytes(const rtw_context* ctx)
 {
     if (!ctx) return 0;
-    size_t g = 0; for (int j = 0; j < RTW_MAX_PARTS; j++) g += ctx->group_ws_bytes[j];
+    size_t g = ctx->denoise_ws_bytes; for (int j = 0; j < RTW_MAX_PARTS; j++) g += ctx->group_ws_bytes[j];
     return (long long)(g + ctx->workspace_bytes);
 }
 int rtw_context_trim(rtw_context* ctx)
@@ -2125,6 +2171,7 @@ int rtw_context_trim(rtw_context* ctx)
         if (ctx->d_group_ws[j]) { (void)hipFree(ctx->d_group_ws[j]); ctx->d_group_ws[j] = nullptr; ctx->group_ws_bytes[j] = 0; ctx->group_clean[j] = false; }
     }
     if (ctx->d_workspace) { (void)hipFree(ctx->d_workspace); ctx->d_workspace = nullptr; ctx->workspace_bytes = 0; ctx->clean_ws = nullptr; }
+    if (ctx->d_denoise_ws) { (void)hipFree(ctx->d_denoise_ws); ctx->d_denoise_ws = nullptr; ctx->denoise_ws_bytes = 0; }
     return RTW_OK;
 }
 int rtw_context_fallbacks(const rtw_context* ctx) { return ctx ? ctx->fallbacks : 0; }
