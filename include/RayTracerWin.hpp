@@ -263,6 +263,15 @@ inline void Denoise(ColorBuffer& Source, FeatureBuffers& Features, ColorBuffer& 
 {
     RtwCheck(rtw_denoise(Source.Get(), Features.Get(), &Params, Destination.Get()));
 }
+// rtw_reproject: the history Hist (HistFeatures, seen by PrevCam) fetched at each pixel's first hit of the current frame (Cur, CurFeatures, CurCam),
+// kept where it shows the same surface and blended with the new sample into Dst, whose count is the history length.  Dst is the next frame's Hist,
+// CurFeatures the next HistFeatures.  Asynchronous, one launch; the formula and the parameters are rtwin.h's.
+inline rtw_reproject_params ReprojectDefaults() { rtw_reproject_params p; RtwCheck(rtw_reproject_default_params(&p)); return p; }
+inline void Reproject(const rtw_camera& CurCam, const rtw_camera& PrevCam, ColorBuffer& Cur, FeatureBuffers& CurFeatures, ColorBuffer& Hist, FeatureBuffers& HistFeatures,
+                      ColorBuffer& Dst, const rtw_reproject_params& Params = ReprojectDefaults())
+{
+    RtwCheck(rtw_reproject(&CurCam, &PrevCam, Cur.Get(), CurFeatures.Get(), Hist.Get(), HistFeatures.Get(), &Params, Dst.Get()));
+}
 
 // ---- Src/RayTracerScene.h --------------------------------------------------------------------------------------------------------
 class RayTracerScene {

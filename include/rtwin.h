@@ -100,6 +100,7 @@ int rtw_context_synchronize(rtw_context* ctx);
  *   "device_build" (1) tree, layouts and screen bins built on the device; "hint_period" (16) pipeline 3: the queue lengths that size the next launches
  *                   are read back every n-th pass; "kernel_timing" 1 = record events around the stages of each pass / group (rtw_last_pass_kernel_ms);
  *   "denoise_tiling" (-1) which tiling each level of rtw_denoise runs: 0 = dense, 1 = lattice, -1 = the measured rule; the result is the same bits;
+ *   "reproject_staging" (-1) where rtw_reproject's taps come from: 0 = global memory, 1 = the block's tap box staged in LDS, -1 = the measured rule; same bits;
  *   "query_kernel"  (-1) which kernel the device queries (rtw_trace_closest_device / rtw_trace_occluded_device / rtw_trace_occluded) run: 1 = the ray-per-lane
  *                   query kernel (rtw_query_kernels.h); 0 = the kernel of rtw_trace_closest on the caller's buffers (any-hit: a closest query whose
  *                   shape >= 0 becomes the byte) -- the A/B baseline and cross-check; -1 = the measured rule (profiles/query_experiments.md): any-hit on
@@ -377,6 +378,49 @@ typedef struct rtw_denoise_params { int levels; float sigma_color, sigma_normal,
  * sigma_normal 0.3 (|n_p - n_q| of about 17 degrees costs a factor e), sigma_depth 0.1 (a relative distance step of 10 % costs a factor e) */
 int rtw_denoise_default_params(rtw_denoise_params* p);
 int rtw_denoise(rtw_framebuffer* src, rtw_features* f, const rtw_denoise_params* p, rtw_framebuffer* dst);
+
+/* ---- temporal reprojection: accumulate frames across camera moves (the temporal half of SVGF, Schied et al. 2017; no reference counterpart) ----
+ * Each pixel's first hit is projected into the previous camera, the history is fetched there, kept only where it shows the same surface, and blended
+ * with the new sample.  It takes buffers and cameras and no scene.  cur / f_cur: the current frame (one or more passes) and its features under cam_cur;
+ * hist / f_hist: the accumulated history and the features of the frame it was made from, under cam_prev; dst: another framebuffer.  The caller keeps two
+ * framebuffers and two feature objects and swaps them each frame: dst is the next frame's hist, f_cur the next f_hist.  A cleared hist means "no history".
+ * dst is an ordinary framebuffer whose count is the history length N: rtw_denoise(dst, f_cur, ...), read, resolve and save all work on it.
+ * Everything is float32 unless stated, every product and sum rounded on its own.  For pixel p = (x, y) of the current frame C, n, z, A, s are as in
+ * rtw_denoise (sums divided by their counts, shape id in its low 30 bits, EPS = 1e-3f); likewise C_q ... s_q of pixel q of the history.  p is EMPTY when
+ * either current count is 0 and BAD when a channel of C is not finite.  EMPTY gives dst.accum = (0, 0, 0, count 0).  W, H = the frame, aspect = (float)W / (float)H.
+ *  1 world point     a = pixel_dx(x, W, aspect) = -(float)(x - W / 2) / (W * 2) * aspect,  b = pixel_dy(y, H) = -(float)(y - H / 2) / (H * 2)   (no sub-sample offset)
+ *                    v = (right_cur * a + up_cur * b) + forward_cur * focal_cur,  dir = v * (1 / sqrtf(v.v)),  P = eye_cur + dir * z
+ *                    Under a lens this is the pinhole's point: the lens blur makes the history approximate, not wrong.
+ *  2 previous frame  d = P - eye_prev,  t = d.forward_prev,  z_exp = sqrtf(d.d);  t <= 0: no history.  Otherwise
+ *                    u = (d.right_prev) * focal_prev / t,  w = (d.up_prev) * focal_prev / t
+ *                    fx = (float)(W / 2) - u * (2 W) / aspect,  fy = (float)(H / 2) - w * (2 H)      (the inverses of pixel_dx / pixel_dy, integer W / 2)
+ *                    a coordinate within 1/64 of an integer is snapped to it: r = rintf(fx); if (fabsf(fx - r) <= 1/64) fx = r -- an unmoved camera then
+ *                    reads exactly one tap, and the result does not hinge on which side of an integer rounding fell.  (a.b = (a.x b.x + a.y b.y) + a.z b.z)
+ *  3 bilinear taps   x0 = floorf(fx), tx = fx - x0, the same for y; the taps (x0, y0), (x0+1, y0), (x0, y0+1), (x0+1, y0+1) in this order with the weights
+ *                    (1-tx)(1-ty), tx(1-ty), (1-tx)ty, tx ty.  A tap of weight 0 is skipped.
+ *  4 validity        a tap q is VALID when it lies in the frame, both history counts are non-zero, C_q is finite, s_q == s_p,
+ *                    depth_tolerance <= 0 or |z_q - z_exp| <= depth_tolerance * z_exp,  and  s_p is a miss or normal_cos <= -1 or n_p.n_q >= normal_cos.
+ *                    Misses are their own surface, as in the denoiser.
+ *  5 history         I_q = C_q / (A_q + EPS) with RTW_REPROJECT_DEMODULATE, else C_q; I_cur likewise.  Over the valid taps in order: sw = sum w,
+ *                    Ih = (sum w I_q) / sw, Nh = the smallest history count (hist.accum's) among them.
+ *  6 blend           history (sw > 0), p not BAD:  N = min(Nh + 1, max_history),  I = Ih + (I_cur - Ih) / (float)N
+ *                    history, p BAD:               I = Ih, N = Nh
+ *                    no history, p not BAD:        I = I_cur, N = 1
+ *                    no history, p BAD:            (0, 0, 0), count 0
+ *                    out = I * (A_cur + EPS) with RTW_REPROJECT_DEMODULATE, else I;  dst.accum = (out * (float)N, int N)
+ *                    dst.argb = the gamma pack of accum.xyz / N, the value a resolve of dst gives; a pixel of count 0 packs as black.
+ * cur, hist and both feature objects are not written.  Asynchronous on the context's stream: ONE launch, no allocation, copy or synchronisation, no work
+ * space.  The context option "reproject_staging" (-1) picks where the taps are read from -- 0 = global memory, 1 = the block's box of taps staged in
+ * LDS, -1 = the faster by measurement -- and never changes a bit.  A NULL camera is the default camera.
+ * RTW_ERR_INVALID, with the destination untouched: a null handle or params, differing sizes, handles of different contexts, dst == cur, dst == hist,
+ * f_cur == f_hist, a camera rtw_scene_set_camera would refuse, a NaN parameter, max_history outside 1..65535, unknown flag bits. */
+#define RTW_REPROJECT_DEMODULATE 1u
+typedef struct rtw_reproject_params { float depth_tolerance, normal_cos; int max_history; uint32_t flags; } rtw_reproject_params;
+/* depth_tolerance 0.05 (the history's distance within 5 % of the expected one), normal_cos 0.9 (normals within about 26 degrees), max_history 32
+ * (from there on an exponential average of weight 1/32), RTW_REPROJECT_DEMODULATE */
+int rtw_reproject_default_params(rtw_reproject_params* p);
+int rtw_reproject(const rtw_camera* cam_cur, const rtw_camera* cam_prev, rtw_framebuffer* cur, rtw_features* f_cur,
+                  rtw_framebuffer* hist, rtw_features* f_hist, const rtw_reproject_params* p, rtw_framebuffer* dst);
 
 /* Device memory the context holds: workspaces + its share of the 201 MB unit-vector table (one copy per device, shared by the contexts on it).
  * The workspace is sized by the largest group of passes rendered (or reserved) so far: per path slot 116 B + 48 B x max_bounce, slots = pixels of the

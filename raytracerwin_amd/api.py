@@ -504,6 +504,28 @@ def denoise(src, features, dst, params=None):
     _check(library().rtw_denoise(src.h, features.h, C.byref(params), dst.h))
 
 
+class ReprojectParams(C.Structure):
+    """rtw_reproject_params; ReprojectParams() holds rtw_reproject_default_params' values (0.05, 0.9, 32, DEMODULATE), keywords override them"""
+    _fields_ = [("depth_tolerance", C.c_float), ("normal_cos", C.c_float), ("max_history", C.c_int), ("flags", C.c_uint32)]
+    DEMODULATE = 1
+
+    def __init__(self, **kw):
+        super().__init__()
+        _check(library().rtw_reproject_default_params(C.byref(self)))
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+def reproject(cam_cur, cam_prev, cur, f_cur, hist, f_hist, dst, params=None):
+    """rtw_reproject: the history Framebuffer hist (its FeatureBuffers f_hist, seen by the Camera cam_prev) fetched at each pixel's first hit of the
+    current frame (cur, f_cur, cam_cur), kept where it shows the same surface and blended with the new sample into the Framebuffer dst, whose count
+    is the history length (the formula is include/rtwin.h's).  dst is the next frame's hist, f_cur the next f_hist.  Created or wrapped buffers
+    alike; a camera may be None (the default camera); asynchronous on the context's stream, one launch."""
+    params = params if params is not None else ReprojectParams()
+    cam = lambda c: None if c is None else C.byref(c)  # noqa: E731
+    _check(library().rtw_reproject(cam(cam_cur), cam(cam_prev), cur.h, f_cur.h, hist.h, f_hist.h, C.byref(params), dst.h))
+
+
 class Camera(C.Structure):
     """rtw_camera: a ray looks from `eye` along (right * (dx + ox) + up * (dy + oy)) + forward * focal, normalized."""
     _fields_ = [("eye", C.c_float * 3), ("right", C.c_float * 3), ("up", C.c_float * 3), ("forward", C.c_float * 3), ("focal", C.c_float)]

@@ -98,6 +98,21 @@ struct DenoiseCall {
 size_t denoise_workspace_bytes(int width, int height);     // two float4 images + the guide records (16 + 4 bytes): 52 bytes per pixel
 bool denoise_level_is_lattice(int tiling, int step);
 int launch_denoise(const DenoiseCall& d, hipStream_t stream);
+// ---- temporal reprojection of a history frame into the current one (rtw_reproject_kernels.h): one launch on `stream`, no workspace ----
+constexpr uint32_t REPROJECT_DEMODULATE = 1u;       // == RTW_REPROJECT_DEMODULATE of rtwin.h
+struct ReprojectCall {
+    const void *cur_accum, *cur_geom, *cur_albedo, *cur_ids;        // the current frame and the history with its features (never written)
+    const void *hist_accum, *hist_geom, *hist_albedo, *hist_ids;
+    void *dst_accum, *dst_argb;
+    const float* gamma_thr;
+    RtwCamera cam_cur, cam_prev;
+    int width, height, max_history;
+    float depth_tolerance, normal_cos;
+    uint32_t flags;
+    int staging;                                // 0 = taps from global memory, 1 = the block's tap box staged in LDS, -1 = the measured rule (reproject_is_staged)
+};
+bool reproject_is_staged(int staging, const RtwCamera& cur, const RtwCamera& prev);
+int launch_reproject(const ReprojectCall& r, hipStream_t stream);
 // ---- KdNode::Build and the layouts derived from the tree, on the device (rtw_build_kernels.h) ----
 struct DeviceBuildIn {      // the arrays RMeshShape owns (host memory)
     const float* points; int n_points; const float* texcoords; int n_texcoords; const float* normals; int n_normals;

@@ -1104,6 +1104,7 @@ __global__ __launch_bounds__(256, 3) void shade_kernel(const RtwSceneDev* __rest
 #include "rtw_group_kernels.h"
 #include "rtw_feature_kernels.h"
 #include "rtw_denoise_kernels.h"
+#include "rtw_reproject_kernels.h"
 #include "rtw_query_kernels.h"
 #include "rtw_build_kernels.h"
 
@@ -1622,6 +1623,34 @@ int launch_denoise(const DenoiseCall& d, hipStream_t stream)
             });
         }
     }
+    return (int)hipGetLastError();
+}
+
+// ---- temporal reprojection (rtw_reproject_kernels.h) ------------------------------------------------------------------------------
+// "reproject_staging" -1, as measured with tools/reproject_bench.py at 1080p and 2160p (profiles/reproject_experiments.md section 2): with an unmoved camera
+// and under a pan the direct variant is 13 to 26 % faster (a tile's taps are the tile plus a border either way, the caches already serve the re-reads, and
+// staging adds the box reduction, two barriers and the LDS round trip); under a dolly and a roll the staged variant is level to 12 % faster.  So: direct
+// when the previous camera has the current one's axes and focal length and its eye moved within the image plane (or not at all), staged otherwise.
+bool reproject_is_staged(int staging, const RtwCamera& cur, const RtwCamera& prev)
+{
+    if (staging >= 0) return staging != 0;
+    const f3 d = mk(prev.eye[0] - cur.eye[0], prev.eye[1] - cur.eye[1], prev.eye[2] - cur.eye[2]);
+    const bool same_axes = memcmp(cur.right, prev.right, 10 * sizeof(float)) == 0;      // right, up, forward, focal
+    return !(same_axes && fabsf(dot(d, mk(cur.forward[0], cur.forward[1], cur.forward[2]))) <= 1e-3f * sqrtf(dot(d, d)));
+}
+
+int launch_reproject(const ReprojectCall& r, hipStream_t stream)
+{
+    ReprojectBufs b;
+    b.cur.accum = (const float4*)r.cur_accum; b.cur.geom = (const float4*)r.cur_geom; b.cur.albedo = (const float4*)r.cur_albedo; b.cur.ids = (const unsigned long long*)r.cur_ids;
+    b.hist.accum = (const float4*)r.hist_accum; b.hist.geom = (const float4*)r.hist_geom; b.hist.albedo = (const float4*)r.hist_albedo; b.hist.ids = (const unsigned long long*)r.hist_ids;
+    b.dst_accum = (float4*)r.dst_accum; b.dst_argb = (uint32_t*)r.dst_argb; b.gamma_thr = r.gamma_thr;
+    b.cam_cur = r.cam_cur; b.cam_prev = r.cam_prev;
+    b.width = r.width; b.height = r.height; b.max_history = r.max_history;
+    b.depth_tolerance = r.depth_tolerance; b.normal_cos = r.normal_cos; b.flags = r.flags;
+    const dim3 grid((unsigned)((r.width + RP_TILE_W - 1) / RP_TILE_W), (unsigned)((r.height + RP_TILE_H - 1) / RP_TILE_H));
+    if (reproject_is_staged(r.staging, r.cam_cur, r.cam_prev)) launch(reproject_kernel<true>, grid, dim3(256), (size_t)RP_BOX_MAX * 36, stream, b);
+    else launch(reproject_kernel<false>, grid, dim3(256), 0, stream, b);
     return (int)hipGetLastError();
 }
 

@@ -92,6 +92,39 @@ RTW_HD void lens_ray(const RtwCamera& c, const float& radius, const float& focus
     dir = mk(w.x * inv, w.y * inv, w.z * inv);
 }
 
+// ---- temporal reprojection (rtw_reproject of rtwin.h, steps 1 to 3) -----------------------------------------------------------------
+// Every product and every sum rounded on its own, in the order written; the tests' NumPy model repeats them.
+// The point the pinhole ray of pixel (x, y) reaches after the distance z (under a lens this is still the pinhole's point)
+RTW_HD f3 reproject_point(const RtwCamera& c, int x, int y, int width, int height, float z)
+{
+    const f3 v = camera_view(c, pixel_dx(x, width, frame_aspect(width, height)), pixel_dy(y, height));
+    const float inv = 1.0f / sqrtf(dot(v, v));
+    return mk(c.eye[0] + (v.x * inv) * z, c.eye[1] + (v.y * inv) * z, c.eye[2] + (v.z * inv) * z);
+}
+// a coordinate within 1/64 of an integer is that integer: an unmoved camera reads exactly one tap, whichever side of it rounding fell
+RTW_HD float reproject_snap(float f) { const float r = rintf(f); return fabsf(f - r) <= 0.015625f ? r : f; }
+// Where camera c sees the point P, in pixels (the inverses of pixel_dx / pixel_dy), and from how far (z_exp); false: P is not in front of it
+RTW_HD bool reproject_project(const RtwCamera& c, f3 P, int width, int height, float& fx, float& fy, float& z_exp)
+{
+    const f3 d = mk(P.x - c.eye[0], P.y - c.eye[1], P.z - c.eye[2]);
+    const float t = dot(d, mk(c.forward[0], c.forward[1], c.forward[2]));
+    z_exp = sqrtf(dot(d, d));
+    if (t <= 0.0f) return false;
+    const float u = dot(d, mk(c.right[0], c.right[1], c.right[2])) * c.focal / t, w = dot(d, mk(c.up[0], c.up[1], c.up[2])) * c.focal / t;
+    fx = reproject_snap((float)(width / 2) - u * (float)(2 * width) / frame_aspect(width, height));
+    fy = reproject_snap((float)(height / 2) - w * (float)(2 * height));
+    return true;
+}
+// The bilinear taps (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1) and their weights (1 - tx)(1 - ty), tx (1 - ty), (1 - tx) ty, tx ty.
+// false: no tap lies in the frame (a coordinate outside [-1, size), or not a number) -- so the conversions to int are always defined
+RTW_HD bool reproject_corner(float fx, float fy, int width, int height, int& x0, int& y0, float& tx, float& ty)
+{
+    if (!(fx >= -1.0f && fx < (float)width && fy >= -1.0f && fy < (float)height)) return false;
+    const float flx = floorf(fx), fly = floorf(fy);
+    x0 = (int)flx; y0 = (int)fly; tx = fx - flx; ty = fy - fly;
+    return true;
+}
+
 // ---- records derived from the tree ------------------------------------------------------------------------------------------------
 // A leaf's triangle with the face normal RRay::TestIntersectionWithTriangle recomputes at every test (Src/RRay.cpp:138-145:
 // normalize(cross(p1 - p0, p2 - p0)), tiny vectors left as they are); it only depends on the triangle

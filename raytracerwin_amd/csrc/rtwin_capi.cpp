@@ -156,6 +156,7 @@ struct rtw_context {
     int denoise_tiling = -1;            // option: each level's tiling: 0 = dense, 1 = lattice, -1 = the measured rule (rtw::denoise_level_is_lattice); same bits either way
     void* d_denoise_ws = nullptr;       // two float4 images + the guide records of the largest frame denoised so far (grown on demand, rtw_context_trim frees it)
     size_t denoise_ws_bytes = 0;
+    int reproject_staging = -1;         // option: rtw_reproject's taps: 0 = from global memory, 1 = the block's tap box staged in LDS, -1 = the measured rule (rtw::reproject_is_staged); same bits either way
 };
 
 struct rtw_scene {
@@ -370,6 +371,7 @@ int rtw_context_set_option(rtw_context* ctx, const char* name, int value)
     }
     if (std::strcmp(name, "query_kernel") == 0) { ctx->query_kernel = value < 0 ? -1 : (value ? 1 : 0); return RTW_OK; }
     if (std::strcmp(name, "denoise_tiling") == 0) { ctx->denoise_tiling = value < 0 ? -1 : (value ? 1 : 0); return RTW_OK; }
+    if (std::strcmp(name, "reproject_staging") == 0) { ctx->reproject_staging = value < 0 ? -1 : (value ? 1 : 0); return RTW_OK; }
     if (std::strcmp(name, "lens_route") == 0) { ctx->lens_route = value < 0 ? -1 : (value ? 1 : 0); return RTW_OK; }
     if (std::strcmp(name, "query_blocks") == 0) { ctx->query_blocks = value < 0 ? 0 : value; return RTW_OK; }
     if (std::strcmp(name, "hint_period") == 0) { ctx->hint_period = value < 1 ? 1 : value; return RTW_OK; }
@@ -2142,6 +2144,47 @@ int rtw_denoise(rtw_framebuffer* src, rtw_features* f, const rtw_denoise_params*
     d.flags = p->flags; d.tiling = cx->denoise_tiling;
     const hipError_t e = (hipError_t)rtw::launch_denoise(d, cx->stream);
     if (e != hipSuccess) return hip_fail(e, "denoise launch");
+    return RTW_OK;
+}
+
+// ---- temporal reprojection (rtw_reproject_kernels.h; the formula is rtwin.h's) ------------------------------------------------------
+static_assert(RTW_REPROJECT_DEMODULATE == rtw::REPROJECT_DEMODULATE, "the kernels' flag bit is the header's");
+int rtw_reproject_default_params(rtw_reproject_params* p)
+{
+    if (!p) return fail(RTW_ERR_INVALID, "null");
+    p->depth_tolerance = 0.05f; p->normal_cos = 0.9f; p->max_history = 32; p->flags = RTW_REPROJECT_DEMODULATE;
+    return RTW_OK;
+}
+
+int rtw_reproject(const rtw_camera* cam_cur, const rtw_camera* cam_prev, rtw_framebuffer* cur, rtw_features* f_cur,
+                  rtw_framebuffer* hist, rtw_features* f_hist, const rtw_reproject_params* p, rtw_framebuffer* dst)
+{
+    if (!cur || !f_cur || !hist || !f_hist || !p || !dst) return fail(RTW_ERR_INVALID, "null argument");
+    if (dst == cur || dst == hist || dst->accum == cur->accum || dst->accum == hist->accum || dst->argb == cur->argb || dst->argb == hist->argb)
+        return fail(RTW_ERR_INVALID, "the destination must be neither the current frame nor the history");
+    if (f_cur == f_hist) return fail(RTW_ERR_INVALID, "the current and the history features are the same object");
+    rtw_context* cx = cur->ctx;
+    if (f_cur->ctx != cx || hist->ctx != cx || f_hist->ctx != cx || dst->ctx != cx) return fail(RTW_ERR_INVALID, "the buffers belong to different contexts");
+    const int W = cur->width, H = cur->height;
+    if (f_cur->width != W || f_cur->height != H || hist->width != W || hist->height != H || f_hist->width != W || f_hist->height != H || dst->width != W || dst->height != H)
+        return fail(RTW_ERR_INVALID, "the buffers differ in size");
+    const RtwCamera cc = cam_cur ? to_internal(*cam_cur) : rtw_default_camera(), cp = cam_prev ? to_internal(*cam_prev) : rtw_default_camera();    // NULL: the default camera, as everywhere
+    if (const char* why = camera_problem(cc)) return fail(RTW_ERR_INVALID, why);
+    if (const char* why = camera_problem(cp)) return fail(RTW_ERR_INVALID, why);
+    if (std::isnan(p->depth_tolerance) || std::isnan(p->normal_cos)) return fail(RTW_ERR_INVALID, "a parameter is NaN");
+    if (p->max_history < 1 || p->max_history > 65535) return fail(RTW_ERR_INVALID, "max_history must be 1..65535");
+    if (p->flags & ~RTW_REPROJECT_DEMODULATE) return fail(RTW_ERR_INVALID, "unknown flag bits");
+    if ((int64_t)W * H > (int64_t)1 << 30) return fail(RTW_ERR_LIMIT, "frame too large");
+    HIP_TRY(hipSetDevice(cx->device));
+    rtw::ReprojectCall r;
+    r.cur_accum = cur->accum; r.cur_geom = f_cur->geom; r.cur_albedo = f_cur->albedo; r.cur_ids = f_cur->ids;
+    r.hist_accum = hist->accum; r.hist_geom = f_hist->geom; r.hist_albedo = f_hist->albedo; r.hist_ids = f_hist->ids;
+    r.dst_accum = dst->accum; r.dst_argb = dst->argb; r.gamma_thr = cx->d_gamma;
+    r.cam_cur = cc; r.cam_prev = cp;
+    r.width = W; r.height = H; r.max_history = p->max_history;
+    r.depth_tolerance = p->depth_tolerance; r.normal_cos = p->normal_cos; r.flags = p->flags; r.staging = cx->reproject_staging;
+    const hipError_t e = (hipError_t)rtw::launch_reproject(r, cx->stream);
+    if (e != hipSuccess) return hip_fail(e, "reproject launch");
     return RTW_OK;
 }
 
