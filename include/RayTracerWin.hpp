@@ -273,6 +273,34 @@ inline void Reproject(const rtw_camera& CurCam, const rtw_camera& PrevCam, Color
     RtwCheck(rtw_reproject(&CurCam, &PrevCam, Cur.Get(), CurFeatures.Get(), Hist.Get(), HistFeatures.Get(), &Params, Dst.Get()));
 }
 
+// Luminance moments (rtw_moments of rtwin.h): per pixel (mu1, mu2), carried by ReprojectMoments and read by DenoiseVariance.  The second constructor
+// wraps device memory the caller owns (width * height * 8 bytes).
+class Moments {
+public:
+    Moments(RtwDevice& dev, int width, int height) : M(nullptr), Width(width), Height(height) { RtwCheck(rtw_moments_create(dev.Get(), width, height, &M)); }
+    Moments(RtwDevice& dev, int width, int height, void* muDev) : M(nullptr), Width(width), Height(height) { RtwCheck(rtw_moments_wrap(dev.Get(), width, height, muDev, &M)); }
+    ~Moments() { rtw_moments_destroy(M); }
+    rtw_moments* Get() const { return M; }
+    void Clear() { RtwCheck(rtw_moments_clear(M)); }
+    void Read(std::vector<float>& mu) { mu.resize((size_t)Width * Height * 2); RtwCheck(rtw_moments_read(M, mu.data())); }      // waits for the device's stream
+    void* DevicePointer() { void* d = nullptr; RtwCheck(rtw_moments_device_pointer(M, &d)); return d; }
+private:
+    Moments(const Moments&); Moments& operator=(const Moments&);
+    rtw_moments* M; int Width, Height;
+};
+// rtw_reproject_moments: Reproject (the same bits in Dst) with the moments carried through the same taps, HistMoments into DstMoments; one launch
+inline void ReprojectMoments(const rtw_camera& CurCam, const rtw_camera& PrevCam, ColorBuffer& Cur, FeatureBuffers& CurFeatures, ColorBuffer& Hist, FeatureBuffers& HistFeatures,
+                             Moments& HistMoments, ColorBuffer& Dst, Moments& DstMoments, const rtw_reproject_params& Params = ReprojectDefaults(), int MomentsHistory = 5)
+{
+    RtwCheck(rtw_reproject_moments(&CurCam, &PrevCam, Cur.Get(), CurFeatures.Get(), Hist.Get(), HistFeatures.Get(), HistMoments.Get(), &Params, MomentsHistory, Dst.Get(), DstMoments.Get()));
+}
+// rtw_denoise_variance: the variance-guided a-trous filter of the reprojected Source (its count is the history length) into Destination
+inline rtw_denoise_variance_params DenoiseVarianceDefaults() { rtw_denoise_variance_params p; RtwCheck(rtw_denoise_variance_default_params(&p)); return p; }
+inline void DenoiseVariance(ColorBuffer& Source, FeatureBuffers& Features, Moments& Mom, ColorBuffer& Destination, const rtw_denoise_variance_params& Params = DenoiseVarianceDefaults())
+{
+    RtwCheck(rtw_denoise_variance(Source.Get(), Features.Get(), Mom.Get(), &Params, Destination.Get()));
+}
+
 // ---- Src/RayTracerScene.h --------------------------------------------------------------------------------------------------------
 class RayTracerScene {
 public:

@@ -100,6 +100,8 @@ int rtw_context_synchronize(rtw_context* ctx);
  *   "device_build" (1) tree, layouts and screen bins built on the device; "hint_period" (16) pipeline 3: the queue lengths that size the next launches
  *                   are read back every n-th pass; "kernel_timing" 1 = record events around the stages of each pass / group (rtw_last_pass_kernel_ms);
  *   "denoise_tiling" (-1) which tiling each level of rtw_denoise runs: 0 = dense, 1 = lattice, -1 = the measured rule; the result is the same bits;
+ *   "variance_prefilter" (-1) where rtw_denoise_variance's levels get the prefiltered variance g from: 0 = fetched by the level kernels, 1 = a prefilter launch
+ *                   per level, -1 = the measured rule; same bits;
  *   "reproject_staging" (-1) where rtw_reproject's taps come from: 0 = global memory, 1 = the block's tap box staged in LDS, -1 = the measured rule; same bits;
  *   "query_kernel"  (-1) which kernel the device queries (rtw_trace_closest_device / rtw_trace_occluded_device / rtw_trace_occluded) run: 1 = the ray-per-lane
  *                   query kernel (rtw_query_kernels.h); 0 = the kernel of rtw_trace_closest on the caller's buffers (any-hit: a closest query whose
@@ -421,6 +423,66 @@ typedef struct rtw_reproject_params { float depth_tolerance, normal_cos; int max
 int rtw_reproject_default_params(rtw_reproject_params* p);
 int rtw_reproject(const rtw_camera* cam_cur, const rtw_camera* cam_prev, rtw_framebuffer* cur, rtw_features* f_cur,
                   rtw_framebuffer* hist, rtw_features* f_hist, const rtw_reproject_params* p, rtw_framebuffer* dst);
+
+/* ---- luminance moments and the variance-guided filter: with rtw_reproject, the whole of SVGF (Schied et al. 2017; no reference counterpart) ----
+ * rtw_denoise weighs colour differences by one fixed sigma_color.  After rtw_reproject a frame is uneven -- pixels with 32 frames of history beside a
+ * disocclusion band of one noisy sample -- and the filter needs to know, per pixel, how noisy the pixel still is.  That estimate is the variance of the
+ * luminance, from moments accumulated through the reprojection, or from the neighbourhood where the history is short.
+ * lum(v) = (0.2126f * v.x + 0.7152f * v.y) + 0.0722f * v.z.
+ *
+ * rtw_moments: width * height float2 (mu1, mu2), the running means of the luminance and of its square.  It carries no count: the history length is the
+ * framebuffer's count, and the caller swaps the two together.  create / wrap (caller-owned device memory, width*height*8 bytes, 8-byte aligned) /
+ * destroy / clear (zeros, asynchronous on the context's stream) / read (mu2 = width*height*2 floats) / device_pointer, as rtw_features. */
+typedef struct rtw_moments rtw_moments;
+int rtw_moments_create(rtw_context* ctx, int width, int height, rtw_moments** out);
+int rtw_moments_wrap(rtw_context* ctx, int width, int height, void* mu_dev, rtw_moments** out);
+int rtw_moments_destroy(rtw_moments* m);
+int rtw_moments_clear(rtw_moments* m);
+int rtw_moments_read(rtw_moments* m, float* mu2);
+int rtw_moments_device_pointer(rtw_moments* m, void** mu_dev);
+/* rtw_reproject with moments, still ONE launch.  dst receives exactly what rtw_reproject writes for the same arguments -- the same bits in accum and
+ * argb, under both settings of "reproject_staging".  For m_dst: l = lum(I_cur) of step 5 (demodulated when the flag is set).  The two-channel image
+ * (l, l * l) is blended by steps 1 to 6 without demodulation, with m_hist as its history image, hist.accum's counts as its history lengths and
+ * moments_history (1..65535; 5 through the wrappers: a floor of 0.2 on the blend weight, as in the paper) in max_history's place.  A tap's validity
+ * is the colour's, so with mu_h = (sum w mu_q) / sw over the colour's valid taps:
+ *     history (sw > 0), p not BAD:   mu = mu_h + ((l, l * l) - mu_h) / (float)min(Nh + 1, moments_history)
+ *     history, p BAD:                mu = mu_h
+ *     no history, p not BAD:         mu = (l, l * l)
+ *     no history and p BAD, or p EMPTY:   mu = (0, 0)
+ * The projection, the taps and their tests are computed once for both.  m_hist is not written.
+ * RTW_ERR_INVALID, with both destinations untouched: whatever rtw_reproject refuses, null moments, moments of another size or context,
+ * m_dst == m_hist, moments_history outside 1..65535. */
+int rtw_reproject_moments(const rtw_camera* cam_cur, const rtw_camera* cam_prev, rtw_framebuffer* cur, rtw_features* f_cur,
+                          rtw_framebuffer* hist, rtw_features* f_hist, rtw_moments* m_hist, const rtw_reproject_params* p, int moments_history,
+                          rtw_framebuffer* dst, rtw_moments* m_dst);
+/* The filter.  C, n, z, A, s, EMPTY, BAD, EPS, I_0, h, the tap order and the skip rules are rtw_denoise's; float32 throughout, every product and sum
+ * rounded on its own, exp(-e) the hardware exp2.  N = src.accum's count, the history length rtw_reproject* left there; (mu1, mu2) = m.
+ * Variance estimate V_0(p), 0 for an empty p:
+ *     N >= min_history:   V_0 = max(mu2 - mu1 * mu1, 0)
+ *     otherwise           s0 = s1 = s2 = 0
+ *                         for dy = -3..3, for dx = -3..3, q = p + (dx, dy)        (in this order)
+ *                             skip q when it is outside the frame, empty or bad, or of another shape with RTW_DENOISE_SAME_SHAPE
+ *                             e = the normal and depth terms of rtw_denoise with this call's sigmas;  w = exp(-e)      (no h, no colour term)
+ *                             s0 += w;  s1 += w * mu1(q);  s2 += w * mu2(q)
+ *                         s0 > 0:  a = s1 / s0,  V_0 = max(s2 / s0 - a * a, 0) * ((float)min_history / (float)N);   else V_0 = 0
+ * Levels i = 0 .. levels-1, step = 2^i, for every non-empty p:
+ *     g(p) = the 3 x 3 prefilter of V_i at distance 1 (not step), dy = -1..1 outer, dx inner, kernel 1/4 centre, 1/8 edges, 1/16 corners;
+ *            skip q when it is outside the frame, empty or bad;  g = (sum k * V_i(q)) / (sum k), 0 when no tap counted
+ *     the 25 taps of rtw_denoise, whose colour term is replaced by:  if sigma_lum > 0 and p is not bad:
+ *            e += |lum(I_i(p)) - lum(I_i(q))| / (sigma_lum * sqrtf(g(p)) + 1e-4f)          (sigma_lum is not halved per level: the variance does that)
+ *     the normal and depth terms, w = h[dx] * h[dy] * exp(-e), sw and sc unchanged;  in addition  sv += (w * w) * V_i(q)
+ *     I_{i+1}(p) by rtw_denoise's three cases;  V_{i+1}(p) = sv / (sw * sw) when sw > 0, else V_i(p)
+ * (The kernels form 1 / (sigma_lum * sqrtf(g) + 1e-4f) once per pixel and multiply, as they do for the depth term.)
+ * Output as rtw_denoise: remodulated, dst.accum = (out, count 1), dst.argb the gamma pack.  src, f and m are not written.  With sigma_lum <= 0 the
+ * variance plays no part and the result equals rtw_denoise's with sigma_color = 0 and the same other parameters bit for bit.
+ * Asynchronous on the context's stream: 1 + levels launches (the estimate includes rtw_denoise's prepare step), levels more with "variance_prefilter" 1.
+ * The work space is rtw_denoise's block of the context (52 bytes per pixel, 56 with "variance_prefilter" 1), counted and trimmed with it.
+ * "denoise_tiling" applies as for rtw_denoise; neither option changes a bit.
+ * RTW_ERR_INVALID: whatever rtw_denoise refuses, a null moments handle, moments of another size or context, min_history outside 1..64. */
+typedef struct rtw_denoise_variance_params { int levels; float sigma_lum, sigma_normal, sigma_depth; uint32_t flags; int min_history; } rtw_denoise_variance_params;
+/* 5 levels, sigma_lum 4 (a luminance step of four standard deviations costs a factor e), sigma_normal 0.3, sigma_depth 0.1, both flags, min_history 4 */
+int rtw_denoise_variance_default_params(rtw_denoise_variance_params* p);
+int rtw_denoise_variance(rtw_framebuffer* src, rtw_features* f, rtw_moments* m, const rtw_denoise_variance_params* p, rtw_framebuffer* dst);
 
 /* Device memory the context holds: workspaces + its share of the 201 MB unit-vector table (one copy per device, shared by the contexts on it).
  * The workspace is sized by the largest group of passes rendered (or reserved) so far: per path slot 116 B + 48 B x max_bounce, slots = pixels of the

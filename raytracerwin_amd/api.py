@@ -526,6 +526,84 @@ def reproject(cam_cur, cam_prev, cur, f_cur, hist, f_hist, dst, params=None):
     _check(library().rtw_reproject(cam(cam_cur), cam(cam_prev), cur.h, f_cur.h, hist.h, f_hist.h, C.byref(params), dst.h))
 
 
+class Moments:
+    """Luminance moments (rtw_moments of include/rtwin.h): per pixel the running means (mu1, mu2) of the luminance and of its square, carried by
+    reproject_moments and read by denoise_variance.  It holds no count: the history length is the framebuffer's, and the two are swapped together."""
+
+    def __init__(self, ctx, width, height, _wrap=None):
+        self.ctx, self.width, self.height = ctx, int(width), int(height)
+        self.h = C.c_void_p()
+        self._tensor = _wrap        # a wrapped torch tensor stays alive with the object
+        ctx._children.add(self)
+        if _wrap is None:
+            _check(library().rtw_moments_create(ctx.h, self.width, self.height, C.byref(self.h)))
+        else:
+            _check(library().rtw_moments_wrap(ctx.h, self.width, self.height, C.c_void_p(_wrap.data_ptr()), C.byref(self.h)))
+
+    @classmethod
+    def wrap(cls, ctx, mu):
+        """Over a contiguous float32 torch tensor (H, W, 2) on the context's device; the kernels write straight into it on the context's stream"""
+        import torch
+        if not (isinstance(mu, torch.Tensor) and mu.is_cuda and mu.is_contiguous() and mu.dtype == torch.float32 and mu.dim() == 3 and mu.shape[2] == 2):
+            raise ValueError("Moments.wrap: mu must be a contiguous float32 torch tensor (H, W, 2) on the context's device")
+        if mu.device.index != ctx.device:
+            raise ValueError("Moments.wrap: the tensor must live on the context's device %d" % ctx.device)
+        return cls(ctx, mu.shape[1], mu.shape[0], _wrap=mu)
+
+    def clear(self):
+        _check(library().rtw_moments_clear(self.h))
+
+    def read(self):
+        """(n, 2) float32 = (mu1, mu2) for the n = width * height pixels; waits for the context's stream"""
+        mu = np.empty((self.width * self.height, 2), np.float32)
+        _check(library().rtw_moments_read(self.h, _p(mu)))
+        return mu
+
+    def device_pointer(self):
+        d = C.c_void_p()
+        _check(library().rtw_moments_device_pointer(self.h, C.byref(d)))
+        return d.value
+
+    def close(self):
+        if getattr(self, "h", None):
+            library().rtw_moments_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def reproject_moments(cam_cur, cam_prev, cur, f_cur, hist, f_hist, m_hist, dst, m_dst, params=None, moments_history=5):
+    """rtw_reproject_moments: reproject (the same bits in dst) with the luminance Moments m_hist carried through the same taps into m_dst, the current
+    sample's (l, l * l) blended in with a history capped at moments_history.  dst and m_dst are the next frame's hist and m_hist.  One launch."""
+    params = params if params is not None else ReprojectParams()
+    cam = lambda c: None if c is None else C.byref(c)  # noqa: E731
+    _check(library().rtw_reproject_moments(cam(cam_cur), cam(cam_prev), cur.h, f_cur.h, hist.h, f_hist.h, m_hist.h, C.byref(params), int(moments_history), dst.h, m_dst.h))
+
+
+class DenoiseVarianceParams(C.Structure):
+    """rtw_denoise_variance_params; DenoiseVarianceParams() holds rtw_denoise_variance_default_params' values (5, 4.0, 0.3, 0.1, both flags, 4)"""
+    _fields_ = [("levels", C.c_int), ("sigma_lum", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("flags", C.c_uint32), ("min_history", C.c_int)]
+    DEMODULATE, SAME_SHAPE = 1, 2
+
+    def __init__(self, **kw):
+        super().__init__()
+        _check(library().rtw_denoise_variance_default_params(C.byref(self)))
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+def denoise_variance(src, features, moments, dst, params=None):
+    """rtw_denoise_variance: the variance-guided a-trous filter (the formula is include/rtwin.h's) of the reprojected Framebuffer src -- whose count is
+    the history length -- guided by the FeatureBuffers and the Moments, into the Framebuffer dst, afterwards an ordinary one-pass framebuffer.
+    Asynchronous on the context's stream."""
+    params = params if params is not None else DenoiseVarianceParams()
+    _check(library().rtw_denoise_variance(src.h, features.h, moments.h, C.byref(params), dst.h))
+
+
 class Camera(C.Structure):
     """rtw_camera: a ray looks from `eye` along (right * (dx + ox) + up * (dy + oy)) + forward * focal, normalized."""
     _fields_ = [("eye", C.c_float * 3), ("right", C.c_float * 3), ("up", C.c_float * 3), ("forward", C.c_float * 3), ("focal", C.c_float)]

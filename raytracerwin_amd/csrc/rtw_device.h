@@ -113,6 +113,25 @@ struct ReprojectCall {
 };
 bool reproject_is_staged(int staging, const RtwCamera& cur, const RtwCamera& prev);
 int launch_reproject(const ReprojectCall& r, hipStream_t stream);
+// ... with luminance moments (rtw_reproject_moments): the same call, the moments variant of the kernel; still one launch.  All three pointers set.
+struct ReprojectMomentsCall { const void* hist; void* dst; int history; };     // float2 (mu1, mu2) per pixel; moments_history
+int launch_reproject_moments(const ReprojectCall& r, const ReprojectMomentsCall& m, hipStream_t stream);
+// ---- the variance-guided a-trous filter (rtw_variance_kernels.h): the estimate (prepare included), then `levels` level launches -- each preceded by a
+// prefilter launch when prefilter_pass is set -- ping-ponging between the workspace's two images, the last one writing dst ----
+struct DenoiseVarianceCall {
+    const void *accum, *geom, *albedo, *ids, *moments;      // the sources (never written)
+    void* workspace;                            // denoise_variance_workspace_bytes(width, height, prefilter_pass)
+    void *dst_accum, *dst_argb;
+    const float* gamma_thr;
+    int width, height, levels, min_history;
+    float sigma_lum, sigma_normal, sigma_depth;
+    uint32_t flags;
+    int tiling;                                 // as DenoiseCall's
+    bool prefilter_pass;                        // g(p) from a pass of its own (true) or fetched by the level kernels (false): denoise_variance_prefilter_is_pass
+};
+size_t denoise_variance_workspace_bytes(int width, int height, bool prefilter_pass);     // rtw_denoise's 52 bytes per pixel, + 4 with the prefilter pass
+bool denoise_variance_prefilter_is_pass(int option);
+int launch_denoise_variance(const DenoiseVarianceCall& d, hipStream_t stream);
 // ---- KdNode::Build and the layouts derived from the tree, on the device (rtw_build_kernels.h) ----
 struct DeviceBuildIn {      // the arrays RMeshShape owns (host memory)
     const float* points; int n_points; const float* texcoords; int n_texcoords; const float* normals; int n_normals;

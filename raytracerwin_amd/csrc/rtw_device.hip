@@ -1105,6 +1105,7 @@ __global__ __launch_bounds__(256, 3) void shade_kernel(const RtwSceneDev* __rest
 #include "rtw_feature_kernels.h"
 #include "rtw_denoise_kernels.h"
 #include "rtw_reproject_kernels.h"
+#include "rtw_variance_kernels.h"
 #include "rtw_query_kernels.h"
 #include "rtw_build_kernels.h"
 
@@ -1639,7 +1640,8 @@ bool reproject_is_staged(int staging, const RtwCamera& cur, const RtwCamera& pre
     return !(same_axes && fabsf(dot(d, mk(cur.forward[0], cur.forward[1], cur.forward[2]))) <= 1e-3f * sqrtf(dot(d, d)));
 }
 
-int launch_reproject(const ReprojectCall& r, hipStream_t stream)
+namespace {
+ReprojectBufs reproject_bufs(const ReprojectCall& r)
 {
     ReprojectBufs b;
     b.cur.accum = (const float4*)r.cur_accum; b.cur.geom = (const float4*)r.cur_geom; b.cur.albedo = (const float4*)r.cur_albedo; b.cur.ids = (const unsigned long long*)r.cur_ids;
@@ -1648,9 +1650,82 @@ int launch_reproject(const ReprojectCall& r, hipStream_t stream)
     b.cam_cur = r.cam_cur; b.cam_prev = r.cam_prev;
     b.width = r.width; b.height = r.height; b.max_history = r.max_history;
     b.depth_tolerance = r.depth_tolerance; b.normal_cos = r.normal_cos; b.flags = r.flags;
+    return b;
+}
+}  // namespace
+
+int launch_reproject(const ReprojectCall& r, hipStream_t stream)
+{
+    const ReprojectBufs b = reproject_bufs(r);
     const dim3 grid((unsigned)((r.width + RP_TILE_W - 1) / RP_TILE_W), (unsigned)((r.height + RP_TILE_H - 1) / RP_TILE_H));
     if (reproject_is_staged(r.staging, r.cam_cur, r.cam_prev)) launch(reproject_kernel<true>, grid, dim3(256), (size_t)RP_BOX_MAX * 36, stream, b);
     else launch(reproject_kernel<false>, grid, dim3(256), 0, stream, b);
+    return (int)hipGetLastError();
+}
+
+// the staged variant's records carry the history's moments: 44 bytes each, RP_BOX_MAX_M of them
+int launch_reproject_moments(const ReprojectCall& r, const ReprojectMomentsCall& mc, hipStream_t stream)
+{
+    const ReprojectBufs b = reproject_bufs(r);
+    ReprojectMoments m;
+    m.hist = (const Mu2*)mc.hist; m.dst = (Mu2*)mc.dst; m.history = mc.history;
+    const dim3 grid((unsigned)((r.width + RP_TILE_W - 1) / RP_TILE_W), (unsigned)((r.height + RP_TILE_H - 1) / RP_TILE_H));
+    if (reproject_is_staged(r.staging, r.cam_cur, r.cam_prev)) launch(reproject_moments_kernel<true>, grid, dim3(256), (size_t)RP_BOX_MAX_M * 44, stream, b, m);
+    else launch(reproject_moments_kernel<false>, grid, dim3(256), 0, stream, b, m);
+    return (int)hipGetLastError();
+}
+
+// ---- the variance-guided a-trous filter (rtw_variance_kernels.h) ----------------------------------------------------------------------
+size_t denoise_variance_workspace_bytes(int width, int height, bool prefilter_pass)
+{
+    return denoise_workspace_bytes(width, height) + (prefilter_pass ? dn_round((size_t)width * (size_t)height * 4) : 0);
+}
+// "variance_prefilter" -1, as measured with tools/variance_bench.py at 1080p and 2160p (profiles/variance_experiments.md section 3)
+bool denoise_variance_prefilter_is_pass(int option) { return option < 0 ? false : option != 0; }
+
+int launch_denoise_variance(const DenoiseVarianceCall& d, hipStream_t stream)
+{
+    const size_t n = (size_t)d.width * (size_t)d.height, img = dn_round(n * 16);
+    char* ws = (char*)d.workspace;
+    float4* image[2] = { (float4*)ws, (float4*)(ws + img) };
+    DenoiseBufs b;
+    b.accum = (const float4*)d.accum; b.geom = (const float4*)d.geom; b.albedo = (const float4*)d.albedo; b.ids = (const unsigned long long*)d.ids;
+    b.guide = (float4*)(ws + 2 * img); b.key = (uint32_t*)(ws + 3 * img);
+    b.dst_accum = (float4*)d.dst_accum; b.dst_argb = (uint32_t*)d.dst_argb; b.gamma_thr = d.gamma_thr;
+    b.width = d.width; b.height = d.height; b.flags = d.flags;
+    VarianceBufs v;
+    v.moments = (const Mu2*)d.moments; v.g = d.prefilter_pass ? (float*)(ws + 3 * img + dn_round(n * 4)) : nullptr;
+    v.min_history = d.min_history; v.sigma_lum = d.sigma_lum > 0.0f ? d.sigma_lum : 0.0f;
+    v.kn = d.sigma_normal > 0.0f ? 1.0f / (d.sigma_normal * d.sigma_normal) : 0.0f;
+    v.kd = d.sigma_depth > 0.0f ? 1.0f / d.sigma_depth : 0.0f;
+    const dim3 tiles((unsigned)((d.width + DN_TILE_W - 1) / DN_TILE_W), (unsigned)((d.height + DN_TILE_H - 1) / DN_TILE_H));
+    launch(variance_estimate_kernel, tiles, dim3(256), 0, stream, b, v, image[0]);
+    const bool pass = d.prefilter_pass && v.sigma_lum > 0.0f;
+    for (int i = 0; i < d.levels; i++) {
+        DenoiseLevel L;
+        L.in = image[i & 1]; L.out = image[(i + 1) & 1]; L.step = 1 << i;
+        L.kc = 0.0f; L.kn = v.kn; L.kd = v.kd;
+        L.tiles_x = L.tiles_y = 0;
+        const bool last = i == d.levels - 1;
+        if (pass) launch(variance_prefilter_kernel, tiles, dim3(256), 0, stream, b, (const float4*)L.in, v.g);
+        if (denoise_level_is_lattice(d.tiling, L.step)) {
+            const int rx = L.step < 4 ? L.step : 4, lw = (d.width + L.step - 1) / L.step, lh = (d.height + L.step - 1) / L.step;
+            L.tiles_x = (lw + 64 / rx - 1) / (64 / rx); L.tiles_y = (lh + DN_LAT_ROWS - 1) / DN_LAT_ROWS;
+            const dim3 grid((unsigned)(L.step / rx * L.tiles_x), (unsigned)(L.step * L.tiles_y));
+            const size_t lds = (size_t)(64 + 4 * rx) * (DN_LAT_ROWS + 4) * 36;
+            with_flags(last, pass, [&](auto LAST, auto GP) {
+                if (rx == 1) launch(variance_level_kernel<DN_LATTICE, 1, decltype(LAST)::value, decltype(GP)::value>, grid, dim3(256), lds, stream, b, L, v);
+                else if (rx == 2) launch(variance_level_kernel<DN_LATTICE, 2, decltype(LAST)::value, decltype(GP)::value>, grid, dim3(256), lds, stream, b, L, v);
+                else launch(variance_level_kernel<DN_LATTICE, 4, decltype(LAST)::value, decltype(GP)::value>, grid, dim3(256), lds, stream, b, L, v);
+            });
+        } else {
+            const size_t lds = (size_t)(DN_TILE_W + 4 * L.step) * (DN_TILE_H + 4 * L.step) * 36;
+            with_flags(last, pass, [&](auto LAST, auto GP) {
+                if (L.step <= 4) launch(variance_level_kernel<DN_DENSE, 1, decltype(LAST)::value, decltype(GP)::value>, tiles, dim3(256), lds, stream, b, L, v);
+                else launch(variance_level_kernel<DN_DIRECT, 1, decltype(LAST)::value, decltype(GP)::value>, tiles, dim3(256), 0, stream, b, L, v);
+            });
+        }
+    }
     return (int)hipGetLastError();
 }
 

@@ -25,6 +25,12 @@
 //   reads per bank at the worst -- for any PW again, since the lanes of a quarter wave share their row.  Nothing is padded.  The 4-byte key reads
 //   come from at most 2 x 64 neighbouring words.
 //   The tail packs ARGB through the gamma thresholds held in LDS, as the denoiser's last level does.
+//   reproject_moments_kernel<STAGED>   rtw_reproject_moments: the same body (reproject_body<STAGED, MOMENTS>) with the luminance moments riding along.  A
+//                              history pixel's record carries its (mu1, mu2) as two more floats -- 44 bytes -- and reproject_taps sums them under the
+//                              colour's weights and validity: the projection, the taps and the tests run once.  The staged box shrinks to
+//                              RP_BOX_MAX_M = 576 records (24.75 KiB, a tile plus a border of 4 x 4 or 8 x 2 pixels), which keeps six blocks to a CU; a
+//                              larger box takes the direct path as before, so the bits do not depend on the limit.  The tail blends (l, l * l) of the
+//                              current sample into the moments by the colour's own cases and writes 8 more bytes.
 
 #define RP_EMPTY 1u         // key bit: one of the pixel's two counts is 0
 #define RP_BAD 2u           // key bit: a channel of the pixel's colour is not finite
@@ -32,6 +38,7 @@
 #define RP_TILE_W 32
 #define RP_TILE_H 8
 #define RP_BOX_MAX 640      // records a block stages at most: 2.5 tiles, e.g. the tile plus a border of 6 x 4 pixels, or a zoom of 1.5
+#define RP_BOX_MAX_M 576    // ... with moments (44-byte records): 2.25 tiles, six blocks to a CU as without
 
 struct ReprojectFrame {     // a framebuffer and its feature buffers
     const float4* __restrict__ accum;       // (sum.xyz, int count)
@@ -50,6 +57,20 @@ struct ReprojectBufs {
     uint32_t flags;                         // REPROJECT_DEMODULATE
 };
 struct RpRecord { float4 c, g; uint32_t key; };
+struct __attribute__((aligned(8))) Mu2 { float x, y; };     // a pixel's luminance moments (mu1, mu2)
+struct ReprojectMoments {   // rtw_reproject_moments: the history's moments, the destination's, and moments_history
+    const Mu2* __restrict__ hist;
+    Mu2* __restrict__ dst;
+    int history;
+};
+struct RpRecordM : RpRecord { Mu2 m; };     // a history record with its moments
+template <bool MOMENTS> struct RpRec { typedef RpRecord type; };
+template <> struct RpRec<true> { typedef RpRecordM type; };
+__device__ __forceinline__ void rp_moments_load(RpRecord&, const Mu2*, int) {}
+__device__ __forceinline__ void rp_moments_load(RpRecordM& q, const Mu2* a, int i) { q.m = a[i]; }
+__device__ __forceinline__ void rp_moments_tap(const RpRecord&, float, Mu2&) {}
+__device__ __forceinline__ void rp_moments_tap(const RpRecordM& q, float w, Mu2& sm) { sm.x += w * q.m.x; sm.y += w * q.m.y; }
+__device__ __forceinline__ float dn_lum(float x, float y, float z) { return (0.2126f * x + 0.7152f * y) + 0.0722f * z; }
 
 // The record of pixel `pixel` of frame f; mod = A + EPS per channel (what a demodulated colour was divided by), zeros for an empty pixel
 __device__ __forceinline__ RpRecord rp_record(const ReprojectFrame& f, int pixel, bool demodulate, f3& mod)
@@ -70,21 +91,22 @@ __device__ __forceinline__ RpRecord rp_record(const ReprojectFrame& f, int pixel
 }
 
 // The four taps of one pixel in the stated order.  fetch(qx, qy, record) hands over the record of the history pixel (qx, qy), and is only asked for
-// pixels inside the frame whose weight is not 0.  sw = the valid taps' weight, s = their weighted colours, nh = the smallest history length among them.
-template <typename Fetch>
+// pixels inside the frame whose weight is not 0.  sw = the valid taps' weight, s = their weighted colours, nh = the smallest history length among them;
+// sm = their weighted moments when the records (Rec) carry any.
+template <typename Rec, typename Fetch>
 __device__ __forceinline__ void reproject_taps(const ReprojectBufs& b, int x0, int y0, float tx, float ty, const RpRecord& p, float z_exp, Fetch&& fetch,
-                                               float& sw, f3& s, int& nh)
+                                               float& sw, f3& s, int& nh, Mu2& sm)
 {
     const bool use_d = b.depth_tolerance > 0.0f, use_n = (p.key >> 2) != 0x3fffffffu && b.normal_cos > -1.0f;      // (a miss has no normal to compare)
     const float zt = b.depth_tolerance * z_exp;
     const float wx[2] = { 1.0f - tx, tx }, wy[2] = { 1.0f - ty, ty };
-    sw = 0.0f; s = mk(0.0f, 0.0f, 0.0f); nh = INT_MAX;
+    sw = 0.0f; s = mk(0.0f, 0.0f, 0.0f); nh = INT_MAX; sm.x = 0.0f; sm.y = 0.0f;
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         const int qx = x0 + (k & 1), qy = y0 + (k >> 1);
         const float w = wx[k & 1] * wy[k >> 1];
         if (w == 0.0f || qx < 0 || qx >= b.width || qy < 0 || qy >= b.height) continue;
-        RpRecord q;
+        Rec q;
         fetch(qx, qy, q);
         bool valid = (q.key & (RP_EMPTY | RP_BAD)) == 0 && ((q.key ^ p.key) >> 2) == 0;
         if (use_d) valid = valid && __builtin_fabsf(q.g.w - z_exp) <= zt;
@@ -93,13 +115,16 @@ __device__ __forceinline__ void reproject_taps(const ReprojectBufs& b, int x0, i
             const int n = __float_as_int(q.c.w);
             sw += w; s.x += w * q.c.x; s.y += w * q.c.y; s.z += w * q.c.z;
             nh = n < nh ? n : nh;
+            rp_moments_tap(q, w, sm);
         }
     }
 }
 
-template <bool STAGED>
-__global__ DN_TARGET __launch_bounds__(256) void reproject_kernel(ReprojectBufs b)
+template <bool STAGED, bool MOMENTS>
+__device__ __forceinline__ DN_TARGET void reproject_body(const ReprojectBufs& b, const ReprojectMoments& m)
 {
+    typedef typename RpRec<MOMENTS>::type Rec;
+    constexpr int BOX = MOMENTS ? RP_BOX_MAX_M : RP_BOX_MAX;
     __shared__ float thr[256];
     __shared__ int box[STAGED ? 16 : 1];            // per wave: min x, min y, max x, max y of its lanes' taps
     const int t = (int)threadIdx.x, W = b.width, H = b.height;
@@ -118,10 +143,11 @@ __global__ DN_TARGET __launch_bounds__(256) void reproject_kernel(ReprojectBufs 
     }
     bool staged = false;
     int bx = 0, by = 0, PW = 0;
-    float4 *lc = nullptr, *lg = nullptr; uint32_t* lk = nullptr;
+    float4 *lc = nullptr, *lg = nullptr; uint32_t* lk = nullptr; Mu2* lm = nullptr;
     if (STAGED) {
-        HIP_DYNAMIC_SHARED(float4, rp_lds);         // [RP_BOX_MAX colour | RP_BOX_MAX geom | RP_BOX_MAX key words]
-        lc = rp_lds; lg = rp_lds + RP_BOX_MAX; lk = (uint32_t*)(rp_lds + 2 * RP_BOX_MAX);
+        HIP_DYNAMIC_SHARED(float4, rp_lds);         // [BOX colour | BOX geom | BOX key words | with moments: BOX moments]
+        lc = rp_lds; lg = rp_lds + BOX; lk = (uint32_t*)(rp_lds + 2 * BOX);
+        if (MOMENTS) lm = (Mu2*)(lk + BOX);
         // this lane's taps of non-zero weight, clipped to the frame (a lane without any takes no part: an inverted interval)
         int lo_x = x0 < 0 ? 0 : x0, hi_x = x0 + (tx > 0.0f ? 1 : 0), lo_y = y0 < 0 ? 0 : y0, hi_y = y0 + (ty > 0.0f ? 1 : 0);
         hi_x = hi_x > W - 1 ? W - 1 : hi_x; hi_y = hi_y > H - 1 ? H - 1 : hi_y;
@@ -140,12 +166,14 @@ __global__ DN_TARGET __launch_bounds__(256) void reproject_kernel(ReprojectBufs 
         const int PH = hi_y >= lo_y ? hi_y - lo_y + 1 : 0;
         PW = hi_x >= lo_x ? hi_x - lo_x + 1 : 0; bx = lo_x; by = lo_y;
         const long long n = (long long)PW * PH;
-        staged = n <= RP_BOX_MAX;
+        staged = n <= BOX;
         if (staged) {
             for (int r = t; r < (int)n; r += 256) {
                 f3 unused;
-                const RpRecord q = rp_record(b.hist, (by + r / PW) * W + bx + r % PW, demodulate, unused);
+                const int hp = (by + r / PW) * W + bx + r % PW;
+                const RpRecord q = rp_record(b.hist, hp, demodulate, unused);
                 lc[r] = q.c; lg[r] = q.g; lk[r] = q.key;
+                if (MOMENTS) lm[r] = m.hist[hp];
             }
             __syncthreads();
         }
@@ -153,17 +181,33 @@ __global__ DN_TARGET __launch_bounds__(256) void reproject_kernel(ReprojectBufs 
         __syncthreads();
     }
     if (!inside) return;
-    float sw = 0.0f; f3 s = mk(0.0f, 0.0f, 0.0f); int nh = INT_MAX;
+    float sw = 0.0f; f3 s = mk(0.0f, 0.0f, 0.0f); int nh = INT_MAX; Mu2 sm = { 0.0f, 0.0f };
     if (taps) {
         if (STAGED && staged)
-            reproject_taps(b, x0, y0, tx, ty, p, z_exp, [&](int qx, int qy, RpRecord& q) {
+            reproject_taps<Rec>(b, x0, y0, tx, ty, p, z_exp, [&](int qx, int qy, Rec& q) {
                 const int r = (qy - by) * PW + (qx - bx);
-                q.c = lc[r]; q.g = lg[r]; q.key = lk[r];
-            }, sw, s, nh);
+                q.c = lc[r]; q.g = lg[r]; q.key = lk[r]; rp_moments_load(q, lm, r);
+            }, sw, s, nh, sm);
         else
-            reproject_taps(b, x0, y0, tx, ty, p, z_exp, [&](int qx, int qy, RpRecord& q) { f3 unused; q = rp_record(b.hist, qy * W + qx, demodulate, unused); }, sw, s, nh);
+            reproject_taps<Rec>(b, x0, y0, tx, ty, p, z_exp, [&](int qx, int qy, Rec& q) {
+                f3 unused; static_cast<RpRecord&>(q) = rp_record(b.hist, qy * W + qx, demodulate, unused); rp_moments_load(q, m.hist, qy * W + qx);
+            }, sw, s, nh, sm);
     }
     const bool pbad = (p.key & RP_BAD) != 0;
+    if (MOMENTS) {                                  // (l, l * l) blended by the colour's cases, moments_history in max_history's place
+        Mu2 mu = { 0.0f, 0.0f };
+        if (!(p.key & RP_EMPTY)) {
+            const float l = dn_lum(p.c.x, p.c.y, p.c.z), l2 = l * l;
+            if (sw > 0.0f) {
+                mu.x = sm.x / sw; mu.y = sm.y / sw;
+                if (!pbad) {
+                    const float nm = (float)(nh >= m.history ? m.history : nh + 1);
+                    mu.x = mu.x + (l - mu.x) / nm; mu.y = mu.y + (l2 - mu.y) / nm;
+                }
+            } else if (!pbad) { mu.x = l; mu.y = l2; }
+        }
+        m.dst[pixel] = mu;
+    }
     f3 I = mk(0.0f, 0.0f, 0.0f); int N = 0;
     if (p.key & RP_EMPTY) {
     } else if (sw > 0.0f) {
@@ -180,3 +224,8 @@ __global__ DN_TARGET __launch_bounds__(256) void reproject_kernel(ReprojectBufs 
     b.dst_accum[pixel] = out;
     b.dst_argb[pixel] = N > 0 ? pack_pixel(thr, mk(out.x / nf, out.y / nf, out.z / nf)) : pack_pixel(thr, mk(0.0f, 0.0f, 0.0f));
 }
+
+template <bool STAGED>
+__global__ DN_TARGET __launch_bounds__(256) void reproject_kernel(ReprojectBufs b) { reproject_body<STAGED, false>(b, ReprojectMoments()); }
+template <bool STAGED>
+__global__ DN_TARGET __launch_bounds__(256) void reproject_moments_kernel(ReprojectBufs b, ReprojectMoments m) { reproject_body<STAGED, true>(b, m); }

@@ -156,6 +156,7 @@ struct rtw_context {
     int denoise_tiling = -1;            // option: each level's tiling: 0 = dense, 1 = lattice, -1 = the measured rule (rtw::denoise_level_is_lattice); same bits either way
     void* d_denoise_ws = nullptr;       // two float4 images + the guide records of the largest frame denoised so far (grown on demand, rtw_context_trim frees it)
     size_t denoise_ws_bytes = 0;
+    int variance_prefilter = -1;        // option: rtw_denoise_variance's g(p): 0 = fetched by the level kernels, 1 = a prefilter pass per level, -1 = the measured rule (rtw::denoise_variance_prefilter_is_pass); same bits either way
     int reproject_staging = -1;         // option: rtw_reproject's taps: 0 = from global memory, 1 = the block's tap box staged in LDS, -1 = the measured rule (rtw::reproject_is_staged); same bits either way
 };
 
@@ -208,6 +209,13 @@ struct rtw_framebuffer {
     int width = 0, height = 0;
     void* accum = nullptr;
     void* argb = nullptr;
+    bool owned = false;
+};
+
+struct rtw_moments {        // luminance moments: float2 (mu1, mu2) per pixel
+    rtw_context* ctx = nullptr;
+    int width = 0, height = 0;
+    void* mu = nullptr;
     bool owned = false;
 };
 
@@ -371,6 +379,7 @@ int rtw_context_set_option(rtw_context* ctx, const char* name, int value)
     }
     if (std::strcmp(name, "query_kernel") == 0) { ctx->query_kernel = value < 0 ? -1 : (value ? 1 : 0); return RTW_OK; }
     if (std::strcmp(name, "denoise_tiling") == 0) { ctx->denoise_tiling = value < 0 ? -1 : (value ? 1 : 0); return RTW_OK; }
+    if (std::strcmp(name, "variance_prefilter") == 0) { ctx->variance_prefilter = value < 0 ? -1 : (value ? 1 : 0); return RTW_OK; }
     if (std::strcmp(name, "reproject_staging") == 0) { ctx->reproject_staging = value < 0 ? -1 : (value ? 1 : 0); return RTW_OK; }
     if (std::strcmp(name, "lens_route") == 0) { ctx->lens_route = value < 0 ? -1 : (value ? 1 : 0); return RTW_OK; }
     if (std::strcmp(name, "query_blocks") == 0) { ctx->query_blocks = value < 0 ? 0 : value; return RTW_OK; }
@@ -2156,8 +2165,9 @@ int rtw_reproject_default_params(rtw_reproject_params* p)
     return RTW_OK;
 }
 
-int rtw_reproject(const rtw_camera* cam_cur, const rtw_camera* cam_prev, rtw_framebuffer* cur, rtw_features* f_cur,
-                  rtw_framebuffer* hist, rtw_features* f_hist, const rtw_reproject_params* p, rtw_framebuffer* dst)
+// rtw_reproject's checks and its call, shared with rtw_reproject_moments
+static int reproject_call(const rtw_camera* cam_cur, const rtw_camera* cam_prev, rtw_framebuffer* cur, rtw_features* f_cur,
+                          rtw_framebuffer* hist, rtw_features* f_hist, const rtw_reproject_params* p, rtw_framebuffer* dst, rtw::ReprojectCall* out)
 {
     if (!cur || !f_cur || !hist || !f_hist || !p || !dst) return fail(RTW_ERR_INVALID, "null argument");
     if (dst == cur || dst == hist || dst->accum == cur->accum || dst->accum == hist->accum || dst->argb == cur->argb || dst->argb == hist->argb)
@@ -2175,16 +2185,149 @@ int rtw_reproject(const rtw_camera* cam_cur, const rtw_camera* cam_prev, rtw_fra
     if (p->max_history < 1 || p->max_history > 65535) return fail(RTW_ERR_INVALID, "max_history must be 1..65535");
     if (p->flags & ~RTW_REPROJECT_DEMODULATE) return fail(RTW_ERR_INVALID, "unknown flag bits");
     if ((int64_t)W * H > (int64_t)1 << 30) return fail(RTW_ERR_LIMIT, "frame too large");
-    HIP_TRY(hipSetDevice(cx->device));
-    rtw::ReprojectCall r;
+    rtw::ReprojectCall& r = *out;
     r.cur_accum = cur->accum; r.cur_geom = f_cur->geom; r.cur_albedo = f_cur->albedo; r.cur_ids = f_cur->ids;
     r.hist_accum = hist->accum; r.hist_geom = f_hist->geom; r.hist_albedo = f_hist->albedo; r.hist_ids = f_hist->ids;
     r.dst_accum = dst->accum; r.dst_argb = dst->argb; r.gamma_thr = cx->d_gamma;
     r.cam_cur = cc; r.cam_prev = cp;
     r.width = W; r.height = H; r.max_history = p->max_history;
     r.depth_tolerance = p->depth_tolerance; r.normal_cos = p->normal_cos; r.flags = p->flags; r.staging = cx->reproject_staging;
+    return RTW_OK;
+}
+
+int rtw_reproject(const rtw_camera* cam_cur, const rtw_camera* cam_prev, rtw_framebuffer* cur, rtw_features* f_cur,
+                  rtw_framebuffer* hist, rtw_features* f_hist, const rtw_reproject_params* p, rtw_framebuffer* dst)
+{
+    rtw::ReprojectCall r;
+    const int rc = reproject_call(cam_cur, cam_prev, cur, f_cur, hist, f_hist, p, dst, &r); if (rc != RTW_OK) return rc;
+    rtw_context* cx = cur->ctx;
+    HIP_TRY(hipSetDevice(cx->device));
     const hipError_t e = (hipError_t)rtw::launch_reproject(r, cx->stream);
     if (e != hipSuccess) return hip_fail(e, "reproject launch");
+    return RTW_OK;
+}
+
+// ---- luminance moments, their reprojection and the variance-guided filter (rtw_reproject_kernels.h, rtw_variance_kernels.h; the formulas are rtwin.h's) ----
+int rtw_moments_create(rtw_context* ctx, int width, int height, rtw_moments** out)
+{
+    if (!ctx || !out || width <= 0 || height <= 0) return fail(RTW_ERR_INVALID, "bad argument");
+    if ((int64_t)width * height > (int64_t)1 << 30) return fail(RTW_ERR_LIMIT, "moments buffer too large");
+    HIP_TRY(hipSetDevice(ctx->device));
+    std::unique_ptr<rtw_moments> m(new rtw_moments());
+    m->ctx = ctx; m->width = width; m->height = height; m->owned = true;
+    const hipError_t e = hipMalloc(&m->mu, (size_t)width * (size_t)height * 8);
+    if (e != hipSuccess) return hip_fail(e, "hipMalloc of the moments buffer");
+    const int rc = rtw_moments_clear(m.get());
+    if (rc != RTW_OK) { (void)hipFree(m->mu); return rc; }
+    *out = m.release();
+    return RTW_OK;
+}
+
+int rtw_moments_wrap(rtw_context* ctx, int width, int height, void* mu_dev, rtw_moments** out)
+{
+    if (!ctx || !out || width <= 0 || height <= 0 || !mu_dev) return fail(RTW_ERR_INVALID, "bad argument");
+    if ((int64_t)width * height > (int64_t)1 << 30) return fail(RTW_ERR_LIMIT, "moments buffer too large");
+    if ((uintptr_t)mu_dev & 7u) return fail(RTW_ERR_INVALID, "the moments must be 8-byte aligned");
+    rtw_moments* m = new rtw_moments();
+    m->ctx = ctx; m->width = width; m->height = height; m->owned = false; m->mu = mu_dev;
+    *out = m;
+    return RTW_OK;
+}
+
+int rtw_moments_destroy(rtw_moments* m)
+{
+    if (!m) return RTW_OK;
+    if (m->owned) {
+        (void)hipSetDevice(m->ctx->device);
+        (void)hipStreamSynchronize(m->ctx->stream);
+        (void)hipFree(m->mu);
+    }
+    delete m;
+    return RTW_OK;
+}
+
+int rtw_moments_clear(rtw_moments* m)
+{
+    if (!m) return fail(RTW_ERR_INVALID, "moments object is null");
+    HIP_TRY(hipSetDevice(m->ctx->device));
+    HIP_TRY(hipMemsetAsync(m->mu, 0, (size_t)m->width * (size_t)m->height * 8, m->ctx->stream));
+    return RTW_OK;
+}
+
+int rtw_moments_read(rtw_moments* m, float* mu2)
+{
+    if (!m || !mu2) return fail(RTW_ERR_INVALID, "null argument");
+    HIP_TRY(hipSetDevice(m->ctx->device));
+    HIP_TRY(hipMemcpyAsync(mu2, m->mu, (size_t)m->width * (size_t)m->height * 8, hipMemcpyDeviceToHost, m->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(m->ctx->stream));
+    return RTW_OK;
+}
+
+int rtw_moments_device_pointer(rtw_moments* m, void** mu_dev)
+{
+    if (!m) return fail(RTW_ERR_INVALID, "moments object is null");
+    if (mu_dev) *mu_dev = m->mu;
+    return RTW_OK;
+}
+
+int rtw_reproject_moments(const rtw_camera* cam_cur, const rtw_camera* cam_prev, rtw_framebuffer* cur, rtw_features* f_cur,
+                          rtw_framebuffer* hist, rtw_features* f_hist, rtw_moments* m_hist, const rtw_reproject_params* p, int moments_history,
+                          rtw_framebuffer* dst, rtw_moments* m_dst)
+{
+    if (!m_hist || !m_dst) return fail(RTW_ERR_INVALID, "null argument");
+    if (m_dst == m_hist || m_dst->mu == m_hist->mu) return fail(RTW_ERR_INVALID, "the destination moments must not be the history's");
+    if (moments_history < 1 || moments_history > 65535) return fail(RTW_ERR_INVALID, "moments_history must be 1..65535");
+    rtw::ReprojectCall r;
+    const int rc = reproject_call(cam_cur, cam_prev, cur, f_cur, hist, f_hist, p, dst, &r); if (rc != RTW_OK) return rc;
+    rtw_context* cx = cur->ctx;
+    if (m_hist->ctx != cx || m_dst->ctx != cx) return fail(RTW_ERR_INVALID, "the moments belong to another context");
+    if (m_hist->width != r.width || m_hist->height != r.height || m_dst->width != r.width || m_dst->height != r.height) return fail(RTW_ERR_INVALID, "the moments differ in size from the frame");
+    HIP_TRY(hipSetDevice(cx->device));
+    rtw::ReprojectMomentsCall m;
+    m.hist = m_hist->mu; m.dst = m_dst->mu; m.history = moments_history;
+    const hipError_t e = (hipError_t)rtw::launch_reproject_moments(r, m, cx->stream);
+    if (e != hipSuccess) return hip_fail(e, "reproject launch");
+    return RTW_OK;
+}
+
+int rtw_denoise_variance_default_params(rtw_denoise_variance_params* p)
+{
+    if (!p) return fail(RTW_ERR_INVALID, "null");
+    p->levels = 5; p->sigma_lum = 4.0f; p->sigma_normal = 0.3f; p->sigma_depth = 0.1f;
+    p->flags = RTW_DENOISE_DEMODULATE | RTW_DENOISE_SAME_SHAPE; p->min_history = 4;
+    return RTW_OK;
+}
+
+int rtw_denoise_variance(rtw_framebuffer* src, rtw_features* f, rtw_moments* m, const rtw_denoise_variance_params* p, rtw_framebuffer* dst)
+{
+    if (!src || !f || !m || !p || !dst) return fail(RTW_ERR_INVALID, "null argument");
+    if (dst == src || dst->accum == src->accum || dst->argb == src->argb) return fail(RTW_ERR_INVALID, "the destination must not be the source");
+    if (src->ctx != f->ctx || src->ctx != dst->ctx || src->ctx != m->ctx) return fail(RTW_ERR_INVALID, "source, features, moments and destination belong to different contexts");
+    if (src->width != f->width || src->height != f->height || src->width != dst->width || src->height != dst->height || src->width != m->width || src->height != m->height)
+        return fail(RTW_ERR_INVALID, "source, features, moments and destination differ in size");
+    if (p->levels < 1 || p->levels > 6) return fail(RTW_ERR_INVALID, "levels must be 1..6");
+    if (std::isnan(p->sigma_lum) || std::isnan(p->sigma_normal) || std::isnan(p->sigma_depth)) return fail(RTW_ERR_INVALID, "a sigma is NaN");
+    if (p->flags & ~(RTW_DENOISE_DEMODULATE | RTW_DENOISE_SAME_SHAPE)) return fail(RTW_ERR_INVALID, "unknown flag bits");
+    if (p->min_history < 1 || p->min_history > 64) return fail(RTW_ERR_INVALID, "min_history must be 1..64");
+    if ((int64_t)src->width * src->height > (int64_t)1 << 30) return fail(RTW_ERR_LIMIT, "frame too large");
+    rtw_context* cx = src->ctx;
+    HIP_TRY(hipSetDevice(cx->device));
+    const bool pass = rtw::denoise_variance_prefilter_is_pass(cx->variance_prefilter);
+    const size_t need = rtw::denoise_variance_workspace_bytes(src->width, src->height, pass);
+    if (need > cx->denoise_ws_bytes) {      // rtw_denoise's block, grow only: an earlier call's launches may still read the old one
+        HIP_TRY(hipStreamSynchronize(cx->stream));
+        if (cx->d_denoise_ws) { (void)hipFree(cx->d_denoise_ws); cx->d_denoise_ws = nullptr; cx->denoise_ws_bytes = 0; }
+        HIP_TRY(hipMalloc(&cx->d_denoise_ws, need));
+        cx->denoise_ws_bytes = need;
+    }
+    rtw::DenoiseVarianceCall d;
+    d.accum = src->accum; d.geom = f->geom; d.albedo = f->albedo; d.ids = f->ids; d.moments = m->mu;
+    d.workspace = cx->d_denoise_ws; d.dst_accum = dst->accum; d.dst_argb = dst->argb; d.gamma_thr = cx->d_gamma;
+    d.width = src->width; d.height = src->height; d.levels = p->levels; d.min_history = p->min_history;
+    d.sigma_lum = p->sigma_lum; d.sigma_normal = p->sigma_normal; d.sigma_depth = p->sigma_depth;
+    d.flags = p->flags; d.tiling = cx->denoise_tiling; d.prefilter_pass = pass;
+    const hipError_t e = (hipError_t)rtw::launch_denoise_variance(d, cx->stream);
+    if (e != hipSuccess) return hip_fail(e, "denoise launch");
     return RTW_OK;
 }
 
