@@ -300,6 +300,13 @@ inline void DenoiseVariance(ColorBuffer& Source, FeatureBuffers& Features, Momen
 {
     RtwCheck(rtw_denoise_variance(Source.Get(), Features.Get(), Mom.Get(), &Params, Destination.Get()));
 }
+// rtw_upsample: the low-resolution Low (LowFeatures) carried to Destination's size under the guidance of the full-size Features of the same camera and
+// remodulated with their base colour.  Destination is 1 to 8 times Low's size at the same aspect.  Asynchronous, one launch.
+inline rtw_upsample_params UpsampleDefaults() { rtw_upsample_params p; RtwCheck(rtw_upsample_default_params(&p)); return p; }
+inline void Upsample(ColorBuffer& Low, FeatureBuffers& LowFeatures, FeatureBuffers& Features, ColorBuffer& Destination, const rtw_upsample_params& Params = UpsampleDefaults())
+{
+    RtwCheck(rtw_upsample(Low.Get(), LowFeatures.Get(), Features.Get(), &Params, Destination.Get()));
+}
 
 // ---- Src/RayTracerScene.h --------------------------------------------------------------------------------------------------------
 class RayTracerScene {

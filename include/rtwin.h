@@ -103,6 +103,7 @@ int rtw_context_synchronize(rtw_context* ctx);
  *   "variance_prefilter" (-1) where rtw_denoise_variance's levels get the prefiltered variance g from: 0 = fetched by the level kernels, 1 = a prefilter launch
  *                   per level, -1 = the measured rule; same bits;
  *   "reproject_staging" (-1) where rtw_reproject's taps come from: 0 = global memory, 1 = the block's tap box staged in LDS, -1 = the measured rule; same bits;
+ *   "upsample_staging" (-1) where rtw_upsample's taps come from: 0 = global memory, 1 = the tile's box of low-resolution records staged in LDS, -1 = the measured rule; same bits;
  *   "query_kernel"  (-1) which kernel the device queries (rtw_trace_closest_device / rtw_trace_occluded_device / rtw_trace_occluded) run: 1 = the ray-per-lane
  *                   query kernel (rtw_query_kernels.h); 0 = the kernel of rtw_trace_closest on the caller's buffers (any-hit: a closest query whose
  *                   shape >= 0 becomes the byte) -- the A/B baseline and cross-check; -1 = the measured rule (profiles/query_experiments.md): any-hit on
@@ -483,6 +484,43 @@ typedef struct rtw_denoise_variance_params { int levels; float sigma_lum, sigma_
 /* 5 levels, sigma_lum 4 (a luminance step of four standard deviations costs a factor e), sigma_normal 0.3, sigma_depth 0.1, both flags, min_history 4 */
 int rtw_denoise_variance_default_params(rtw_denoise_variance_params* p);
 int rtw_denoise_variance(rtw_framebuffer* src, rtw_features* f, rtw_moments* m, const rtw_denoise_variance_params* p, rtw_framebuffer* dst);
+
+/* ---- guided upsampling: a low-resolution frame to full size by its features (joint bilateral upsampling, Kopf et al. 2007; no reference counterpart) ----
+ * Render, reproject and filter at a fraction of the frame, then carry the result to full size: the filtered signal is low-frequency (the base colour is
+ * divided out), and what is sharp in the final frame -- depth and normal edges, shape boundaries, texture detail -- comes from full-size feature buffers,
+ * which are cheap.  It takes buffers and no scene.  lo / f_lo: the low-resolution frame and its features, w x h; f_hi: the features of the same camera at
+ * W x H; dst: a W x H framebuffer.  Accepted: w <= W <= 8 w, W * h == H * w (the same aspect, exact in integers), W, H <= 16384; equal sizes are allowed.
+ * Everything is float32 unless stated, every product and sum rounded on its own.  C, n, z, A, s, EPS = 1e-3f and the low 30 bits of a shape id are as in
+ * rtw_denoise: for a low pixel q they come from lo and f_lo, for a full-size pixel p = (x, y) from f_hi (n_p, z_p, A_p, s_p).  p is EMPTY when f_hi's count
+ * is 0: dst.accum = (0, 0, 0, count 0).  q is EMPTY when either of its counts is 0 and BAD when a channel of C_q is not finite.
+ * I_q = C_q / (A_q + EPS) with RTW_UPSAMPLE_DEMODULATE, else C_q.
+ *  1 tap corner      in integers: the screen point of pixel x of a W-wide frame is (x - W / 2) / W with integer W / 2, as in pixel_dx (no sub-sample offset,
+ *                    as in rtw_reproject).  nx = (x - W / 2) * w,  kx = floor(nx / W) (floor division, negative values included),  x0 = kx + w / 2,
+ *                    tx = (float)(nx - kx * W) / (float)W; the same for y with H and h.  With equal sizes x0 = x and tx = 0; at an integer ratio every
+ *                    ratio-th pixel lands on a low pixel exactly.
+ *  2 tap error       e(q) = |n_p - n_q|^2 / sigma_normal^2 + ((z_p - z_q) / (sigma_depth * max(|z_p|, 1e-6)))^2, a term off for a non-positive sigma;
+ *                    exp(-e) is the hardware exp2 of -e * log2(e), as in the denoiser.  A tap is SKIPPED when it is outside the low frame, EMPTY or BAD,
+ *                    or when RTW_UPSAMPLE_SAME_SHAPE is set and s_q != s_p.  Misses are their own surface.
+ *  3 round 1         the taps (x0, y0), (x0+1, y0), (x0, y0+1), (x0+1, y0+1) in this order, b = (1-tx)(1-ty), tx(1-ty), (1-tx)ty, tx ty; a tap with b == 0
+ *                    is skipped.  w = b * exp(-e);  sw += w;  sc += w * I_q.  Accepted when sw >= SW_MIN = 1e-3f: I = sc / sw.
+ *  4 round 2         only when round 1 is not accepted (a thin feature or a silhouette that no bilinear tap shows): dy = -1..2 outer, dx = -1..2 inner, the
+ *                    taps (x0+dx, y0+dy),  w = k[dx] * k[dy] * exp(-e) with k = (1/8, 3/8, 3/8, 1/8); the same skip rule, the same acceptance.
+ *  5 round 3         only when round 2 is not accepted: among the four positions of round 1, the one that is in the frame, not EMPTY and not BAD,
+ *                    whatever its shape, with the largest b (the first in order on ties; a position of b == 0 counts here).  I = I_q of that tap.
+ *                    None: dst.accum = (0, 0, 0, count 0).
+ *  6 output          out = I * (A_p + EPS) with RTW_UPSAMPLE_DEMODULATE, else I;  dst.accum = (out, count 1);  dst.argb = the gamma pack of out; a pixel of
+ *                    count 0 packs as black.  dst is then an ordinary one-pass framebuffer for every other call.
+ * lo, f_lo and f_hi are not written.  Asynchronous on the context's stream: ONE launch, no work space, no allocation, copy or synchronisation.  The context
+ * option "upsample_staging" (-1) picks where the taps are read from -- 0 = global memory, 1 = the tile's box of low-resolution records staged in LDS,
+ * -1 = the faster by measurement -- and never changes a bit.
+ * RTW_ERR_INVALID, with dst untouched: a null handle or params, a shape outside the rule above, f_lo not of lo's size, dst not of f_hi's size, handles of
+ * different contexts, dst == lo, f_lo == f_hi, a NaN sigma, unknown flag bits. */
+#define RTW_UPSAMPLE_DEMODULATE 1u
+#define RTW_UPSAMPLE_SAME_SHAPE 2u
+typedef struct rtw_upsample_params { float sigma_normal, sigma_depth; uint32_t flags; } rtw_upsample_params;
+/* sigma_normal 0.3, sigma_depth 0.1 (they mean what they mean in rtw_denoise), both flags */
+int rtw_upsample_default_params(rtw_upsample_params* p);
+int rtw_upsample(rtw_framebuffer* lo, rtw_features* f_lo, rtw_features* f_hi, const rtw_upsample_params* p, rtw_framebuffer* dst);
 
 /* Device memory the context holds: workspaces + its share of the 201 MB unit-vector table (one copy per device, shared by the contexts on it).
  * The workspace is sized by the largest group of passes rendered (or reserved) so far: per path slot 116 B + 48 B x max_bounce, slots = pixels of the

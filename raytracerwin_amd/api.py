@@ -526,6 +526,27 @@ def reproject(cam_cur, cam_prev, cur, f_cur, hist, f_hist, dst, params=None):
     _check(library().rtw_reproject(cam(cam_cur), cam(cam_prev), cur.h, f_cur.h, hist.h, f_hist.h, C.byref(params), dst.h))
 
 
+class UpsampleParams(C.Structure):
+    """rtw_upsample_params; UpsampleParams() holds rtw_upsample_default_params' values (0.3, 0.1, both flags), keywords override them"""
+    _fields_ = [("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("flags", C.c_uint32)]
+    DEMODULATE, SAME_SHAPE = 1, 2
+
+    def __init__(self, **kw):
+        super().__init__()
+        _check(library().rtw_upsample_default_params(C.byref(self)))
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+def upsample(lo, f_lo, f_hi, dst, params=None):
+    """rtw_upsample: the low-resolution Framebuffer lo (its FeatureBuffers f_lo) carried to the size of the Framebuffer dst under the guidance of the
+    full-size FeatureBuffers f_hi of the same camera, and remodulated with their base colour (the formula is include/rtwin.h's).  dst is 1 to 8 times
+    lo's size at the same aspect and afterwards an ordinary one-pass framebuffer.  Created or wrapped buffers alike; asynchronous on the context's
+    stream, one launch."""
+    params = params if params is not None else UpsampleParams()
+    _check(library().rtw_upsample(lo.h, f_lo.h, f_hi.h, C.byref(params), dst.h))
+
+
 class Moments:
     """Luminance moments (rtw_moments of include/rtwin.h): per pixel the running means (mu1, mu2) of the luminance and of its square, carried by
     reproject_moments and read by denoise_variance.  It holds no count: the history length is the framebuffer's, and the two are swapped together."""

@@ -116,6 +116,20 @@ int launch_reproject(const ReprojectCall& r, hipStream_t stream);
 // ... with luminance moments (rtw_reproject_moments): the same call, the moments variant of the kernel; still one launch.  All three pointers set.
 struct ReprojectMomentsCall { const void* hist; void* dst; int history; };     // float2 (mu1, mu2) per pixel; moments_history
 int launch_reproject_moments(const ReprojectCall& r, const ReprojectMomentsCall& m, hipStream_t stream);
+// ---- guided upsampling of a low-resolution framebuffer under full-size features (rtw_upsample_kernels.h): one launch on `stream`, no workspace ----
+constexpr uint32_t UPSAMPLE_DEMODULATE = 1u, UPSAMPLE_SAME_SHAPE = 2u;    // == RTW_UPSAMPLE_* of rtwin.h
+struct UpsampleCall {
+    const void *lo_accum, *lo_geom, *lo_albedo, *lo_ids;            // the low-resolution frame and its features (never written)
+    const void *hi_geom, *hi_albedo, *hi_ids;                       // the full-size features (never written)
+    void *dst_accum, *dst_argb;
+    const float* gamma_thr;
+    int width, height, lo_width, lo_height;     // lo_width <= width <= 8 lo_width, width * lo_height == height * lo_width, width and height <= 16384
+    float sigma_normal, sigma_depth;
+    uint32_t flags;
+    int staging;                                // 0 = taps from global memory, 1 = the tile's box of low-resolution records staged in LDS, -1 = the measured rule (upsample_is_staged)
+};
+bool upsample_is_staged(int staging);
+int launch_upsample(const UpsampleCall& u, hipStream_t stream);
 // ---- the variance-guided a-trous filter (rtw_variance_kernels.h): the estimate (prepare included), then `levels` level launches -- each preceded by a
 // prefilter launch when prefilter_pass is set -- ping-ponging between the workspace's two images, the last one writing dst ----
 struct DenoiseVarianceCall {

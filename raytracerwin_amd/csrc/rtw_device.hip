@@ -1106,6 +1106,7 @@ __global__ __launch_bounds__(256, 3) void shade_kernel(const RtwSceneDev* __rest
 #include "rtw_denoise_kernels.h"
 #include "rtw_reproject_kernels.h"
 #include "rtw_variance_kernels.h"
+#include "rtw_upsample_kernels.h"
 #include "rtw_query_kernels.h"
 #include "rtw_build_kernels.h"
 
@@ -1672,6 +1673,30 @@ int launch_reproject_moments(const ReprojectCall& r, const ReprojectMomentsCall&
     const dim3 grid((unsigned)((r.width + RP_TILE_W - 1) / RP_TILE_W), (unsigned)((r.height + RP_TILE_H - 1) / RP_TILE_H));
     if (reproject_is_staged(r.staging, r.cam_cur, r.cam_prev)) launch(reproject_moments_kernel<true>, grid, dim3(256), (size_t)RP_BOX_MAX_M * 44, stream, b, m);
     else launch(reproject_moments_kernel<false>, grid, dim3(256), 0, stream, b, m);
+    return (int)hipGetLastError();
+}
+
+// ---- guided upsampling (rtw_upsample_kernels.h) -----------------------------------------------------------------------------------------
+// "upsample_staging" -1, as measured with tools/upsample_bench.py at ratios 2, 3 and 4 into 1080p and 2160p (profiles/upsample_experiments.md section 2):
+// the staged variant is 23 to 41 % faster in all six -- the direct one makes a record (ten divisions, 56 bytes from L2) per tap, the staged one 0.6 per
+// output at most, and its box needs no reduction.  So: always staged.
+bool upsample_is_staged(int staging) { return staging < 0 ? true : staging != 0; }
+
+int launch_upsample(const UpsampleCall& u, hipStream_t stream)
+{
+    UpsampleBufs b;
+    b.lo.accum = (const float4*)u.lo_accum; b.lo.geom = (const float4*)u.lo_geom; b.lo.albedo = (const float4*)u.lo_albedo; b.lo.ids = (const unsigned long long*)u.lo_ids;
+    b.geom = (const float4*)u.hi_geom; b.albedo = (const float4*)u.hi_albedo; b.ids = (const unsigned long long*)u.hi_ids;
+    b.dst_accum = (float4*)u.dst_accum; b.dst_argb = (uint32_t*)u.dst_argb; b.gamma_thr = u.gamma_thr;
+    b.W = u.width; b.H = u.height; b.w = u.lo_width; b.h = u.lo_height;
+    b.kn = u.sigma_normal > 0.0f ? 1.0f / (u.sigma_normal * u.sigma_normal) : 0.0f;
+    b.kd = u.sigma_depth > 0.0f ? 1.0f / u.sigma_depth : 0.0f;
+    b.flags = u.flags;
+    // the staged variant's box of UP_BOX records holds a tile's taps only under these (rtw_upsample refuses anything else)
+    if (u.lo_width < 1 || u.lo_height < 1 || u.lo_width > u.width || u.lo_height > u.height) return (int)hipErrorInvalidValue;
+    const dim3 grid((unsigned)((u.width + UP_TILE_W - 1) / UP_TILE_W), (unsigned)((u.height + UP_TILE_H - 1) / UP_TILE_H));
+    if (upsample_is_staged(u.staging)) launch(upsample_kernel<true>, grid, dim3(256), 0, stream, b);
+    else launch(upsample_kernel<false>, grid, dim3(256), 0, stream, b);
     return (int)hipGetLastError();
 }
 

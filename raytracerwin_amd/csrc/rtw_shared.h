@@ -125,6 +125,19 @@ RTW_HD bool reproject_corner(float fx, float fy, int width, int height, int& x0,
     return true;
 }
 
+// ---- guided upsampling (rtw_upsample of rtwin.h, step 1) ------------------------------------------------------------------------------
+// Pixel x of a `size`-wide frame looks through the screen point (x - size / 2) / size (pixel_dx without its sign and scale); in a `low`-wide frame
+// of the same camera that point lies tx of the way from pixel x0 to pixel x0 + 1.  Integers up to the last division: n = (x - size / 2) * low,
+// k = floor(n / size), x0 = k + low / 2, tx = (n - k * size) / size in [0, 1).  size, low <= 16384, so n fits an int32.
+RTW_HD void upsample_corner(int x, int size, int low, int& x0, float& tx)
+{
+    const int n = (x - size / 2) * low;
+    int k = n / size;
+    if (n - k * size < 0) k--;              // C's division truncates: floor for a negative n
+    x0 = k + low / 2;
+    tx = (float)(n - k * size) / (float)size;
+}
+
 // ---- records derived from the tree ------------------------------------------------------------------------------------------------
 // A leaf's triangle with the face normal RRay::TestIntersectionWithTriangle recomputes at every test (Src/RRay.cpp:138-145:
 // normalize(cross(p1 - p0, p2 - p0)), tiny vectors left as they are); it only depends on the triangle

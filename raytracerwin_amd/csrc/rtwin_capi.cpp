@@ -158,6 +158,7 @@ struct rtw_context {
     size_t denoise_ws_bytes = 0;
     int variance_prefilter = -1;        // option: rtw_denoise_variance's g(p): 0 = fetched by the level kernels, 1 = a prefilter pass per level, -1 = the measured rule (rtw::denoise_variance_prefilter_is_pass); same bits either way
     int reproject_staging = -1;         // option: rtw_reproject's taps: 0 = from global memory, 1 = the block's tap box staged in LDS, -1 = the measured rule (rtw::reproject_is_staged); same bits either way
+    int upsample_staging = -1;          // option: rtw_upsample's taps: 0 = from global memory, 1 = the tile's box of low-resolution records staged in LDS, -1 = the measured rule (rtw::upsample_is_staged); same bits either way
 };
 
 struct rtw_scene {
@@ -381,6 +382,7 @@ int rtw_context_set_option(rtw_context* ctx, const char* name, int value)
     if (std::strcmp(name, "denoise_tiling") == 0) { ctx->denoise_tiling = value < 0 ? -1 : (value ? 1 : 0); return RTW_OK; }
     if (std::strcmp(name, "variance_prefilter") == 0) { ctx->variance_prefilter = value < 0 ? -1 : (value ? 1 : 0); return RTW_OK; }
     if (std::strcmp(name, "reproject_staging") == 0) { ctx->reproject_staging = value < 0 ? -1 : (value ? 1 : 0); return RTW_OK; }
+    if (std::strcmp(name, "upsample_staging") == 0) { ctx->upsample_staging = value < 0 ? -1 : (value ? 1 : 0); return RTW_OK; }
     if (std::strcmp(name, "lens_route") == 0) { ctx->lens_route = value < 0 ? -1 : (value ? 1 : 0); return RTW_OK; }
     if (std::strcmp(name, "query_blocks") == 0) { ctx->query_blocks = value < 0 ? 0 : value; return RTW_OK; }
     if (std::strcmp(name, "hint_period") == 0) { ctx->hint_period = value < 1 ? 1 : value; return RTW_OK; }
@@ -2328,6 +2330,42 @@ int rtw_denoise_variance(rtw_framebuffer* src, rtw_features* f, rtw_moments* m, 
     d.flags = p->flags; d.tiling = cx->denoise_tiling; d.prefilter_pass = pass;
     const hipError_t e = (hipError_t)rtw::launch_denoise_variance(d, cx->stream);
     if (e != hipSuccess) return hip_fail(e, "denoise launch");
+    return RTW_OK;
+}
+
+// ---- guided upsampling (rtw_upsample_kernels.h; the formula is rtwin.h's) -------------------------------------------------------------
+static_assert(RTW_UPSAMPLE_DEMODULATE == rtw::UPSAMPLE_DEMODULATE && RTW_UPSAMPLE_SAME_SHAPE == rtw::UPSAMPLE_SAME_SHAPE, "the kernels' flag bits are the header's");
+int rtw_upsample_default_params(rtw_upsample_params* p)
+{
+    if (!p) return fail(RTW_ERR_INVALID, "null");
+    p->sigma_normal = 0.3f; p->sigma_depth = 0.1f; p->flags = RTW_UPSAMPLE_DEMODULATE | RTW_UPSAMPLE_SAME_SHAPE;
+    return RTW_OK;
+}
+
+int rtw_upsample(rtw_framebuffer* lo, rtw_features* f_lo, rtw_features* f_hi, const rtw_upsample_params* p, rtw_framebuffer* dst)
+{
+    if (!lo || !f_lo || !f_hi || !p || !dst) return fail(RTW_ERR_INVALID, "null argument");
+    if (dst == lo || dst->accum == lo->accum || dst->argb == lo->argb) return fail(RTW_ERR_INVALID, "the destination must not be the low-resolution frame");
+    if (f_lo == f_hi) return fail(RTW_ERR_INVALID, "the low-resolution and the full-size features are the same object");
+    rtw_context* cx = lo->ctx;
+    if (f_lo->ctx != cx || f_hi->ctx != cx || dst->ctx != cx) return fail(RTW_ERR_INVALID, "the buffers belong to different contexts");
+    const int w = lo->width, h = lo->height, W = dst->width, H = dst->height;
+    if (f_lo->width != w || f_lo->height != h) return fail(RTW_ERR_INVALID, "the low-resolution frame and its features differ in size");
+    if (f_hi->width != W || f_hi->height != H) return fail(RTW_ERR_INVALID, "the destination and the full-size features differ in size");
+    if (W > 16384 || H > 16384) return fail(RTW_ERR_INVALID, "the destination is larger than 16384 x 16384");
+    if (w > W || W > 8 * w) return fail(RTW_ERR_INVALID, "the destination must be 1 to 8 times as wide as the low-resolution frame");
+    if ((int64_t)W * h != (int64_t)H * w) return fail(RTW_ERR_INVALID, "the two frames differ in aspect");
+    if (std::isnan(p->sigma_normal) || std::isnan(p->sigma_depth)) return fail(RTW_ERR_INVALID, "a sigma is NaN");
+    if (p->flags & ~(RTW_UPSAMPLE_DEMODULATE | RTW_UPSAMPLE_SAME_SHAPE)) return fail(RTW_ERR_INVALID, "unknown flag bits");
+    HIP_TRY(hipSetDevice(cx->device));
+    rtw::UpsampleCall u;
+    u.lo_accum = lo->accum; u.lo_geom = f_lo->geom; u.lo_albedo = f_lo->albedo; u.lo_ids = f_lo->ids;
+    u.hi_geom = f_hi->geom; u.hi_albedo = f_hi->albedo; u.hi_ids = f_hi->ids;
+    u.dst_accum = dst->accum; u.dst_argb = dst->argb; u.gamma_thr = cx->d_gamma;
+    u.width = W; u.height = H; u.lo_width = w; u.lo_height = h;
+    u.sigma_normal = p->sigma_normal; u.sigma_depth = p->sigma_depth; u.flags = p->flags; u.staging = cx->upsample_staging;
+    const hipError_t e = (hipError_t)rtw::launch_upsample(u, cx->stream);
+    if (e != hipSuccess) return hip_fail(e, "upsample launch");
     return RTW_OK;
 }
 
