@@ -113,7 +113,9 @@ int rtw_context_synchronize(rtw_context* ctx);
  *   "lens_route"    (-1) pipeline 4, scenes with a lens (rtw_scene_set_lens): 1 = the camera round -- glens_kernel makes the lens rays, a lane per path, and
  *                   the ray-per-lane trace kernels of the bounce rounds find their hits in a round of its own ahead of round 0; 0 = gprimary_kernel's LENS
  *                   instantiation, which walks the trees itself a tile per wave; -1 = the measured rule (profiles/lens_experiments.md): route 0, which
- *                   won on every scene measured -- the camera round is kept as the cross-check.  Results never depend on it. */
+ *                   won on every scene measured -- the camera round is kept as the cross-check.  Results never depend on it;
+ *   "material_variants" (1) pipeline 4: the shade and primary kernels are instantiated for the scene's material class (RTW_MATERIAL_CLASS_*, worked out by
+ *                   rtw_scene_commit); 0 = the general instantiation for every scene, the A/B baseline and cross-check.  Results never depend on it. */
 int rtw_context_set_option(rtw_context* ctx, const char* name, int value);
 /* with option "kernel_timing" = 1: HIP-event durations (ms) of the latest pass's three stages -- primary kernel(s),
  * the per-bounce trace / shade launches, resolve -- measured on the context's stream; waits for that pass. */
@@ -122,6 +124,15 @@ int rtw_last_pass_kernel_ms(rtw_context* ctx, float out3[3]);
 int rtw_last_group_passes(rtw_context* ctx);
 /* the pipeline the latest render call of this context actually ran (0, 3 or 4; -1 before the first call): lets a caller see a fallback */
 int rtw_last_pass_pipeline(rtw_context* ctx);
+/* Material classes.  FLAT: every shape of the scene has a material tree of exactly one node, a Diffuse or a DiffuseChecker, and no mesh has a valid
+ * texture; FLAT_TEX: the same trees, some mesh textured; GENERAL: every other scene -- and every call with work counters on (rtw_stats_enable), with a
+ * sphere / plane / capsule / triangle in the scene or with a lens, for which no specialised kernels are built. */
+#define RTW_MATERIAL_CLASS_GENERAL 0
+#define RTW_MATERIAL_CLASS_FLAT 1
+#define RTW_MATERIAL_CLASS_FLAT_TEX 2
+/* the material class the shade / primary kernels of the latest pipeline-4 call of this context were instantiated for (-1 before the first such call):
+ * lets a caller see that a flat scene did get its kernels, and that option "material_variants" 0 did switch them off */
+int rtw_last_pass_material_class(rtw_context* ctx);
 const char* rtw_last_error(void);
 const char* rtw_version(void);
 

@@ -12,6 +12,7 @@ from .api import (  # noqa: F401
     Camera, Comm, Context, DenoiseParams, DenoiseVarianceParams, FeatureBuffers, Framebuffer, Lens, Moments, RayTracerScene, ReprojectParams, UpsampleParams, camera_rays, denoise, denoise_variance, lens_rays, reproject, reproject_moments, upsample, RCapsule, RMeshShape, RPlane, RSphere, RTriangle, RenderOption, RtwError,
     SurfaceMaterial_Blend, SurfaceMaterial_Combine, SurfaceMaterial_Diffuse, SurfaceMaterial_DiffuseChecker,
     SurfaceMaterial_Emissive, SurfaceMaterial_Null, SurfaceMaterial_Reflective,
+    MATERIAL_CLASS_FLAT, MATERIAL_CLASS_FLAT_TEX, MATERIAL_CLASS_GENERAL,
     ThreadWorker_Render, build_library, library, library_path, material_nodes_from_array, png_load,
 )
 

@@ -13,6 +13,7 @@ _LIB = os.environ.get("RTW_LIB") or os.path.join(_HERE, "librtwin.so")      # RT
 MATERIAL_DTYPE = np.dtype([("type", "<i4"), ("r", "<f4"), ("g", "<f4"), ("b", "<f4"), ("param", "<f4"),
                            ("child_a", "<i4"), ("child_b", "<i4"), ("pad", "<i4")])
 MAT_DIFFUSE, MAT_DIFFUSE_CHECKER, MAT_REFLECTIVE, MAT_EMISSIVE, MAT_BLEND, MAT_COMBINE, MAT_NULL = range(7)
+MATERIAL_CLASS_GENERAL, MATERIAL_CLASS_FLAT, MATERIAL_CLASS_FLAT_TEX = range(3)       # Context.last_pass_material_class()
 
 
 class RtwError(RuntimeError):
@@ -287,6 +288,10 @@ class Context:
     def last_pass_pipeline(self):
         """the pipeline the latest render call actually ran (a fallback shows here)"""
         return int(library().rtw_last_pass_pipeline(self.h))
+
+    def last_pass_material_class(self):
+        """the material class (MATERIAL_CLASS_*) the latest pipeline-4 call's shade / primary kernels were instantiated for; -1 before the first"""
+        return int(library().rtw_last_pass_material_class(self.h))
 
     def memory_bytes(self):
         """device memory the context holds (workspaces + its share of the unit-vector table)"""

@@ -45,8 +45,17 @@ inline size_t group_capacity(size_t paths_per_pass, int n_passes) { return paths
 struct GroupLayout { size_t counters_off, rad_off, state_off, hit_off, carry_off, levels_off, list0_off, list1_off, overflow_off, tlist0_off, tlist1_off, total; };
 // device bytes of a group's workspace: `capacity` path slots (busy tiles x 64 x sub-samples x passes of the group, rounded up to a power of two of passes)
 size_t group_workspace_bytes(size_t capacity, int max_bounce, bool carry, GroupLayout* out);
+// The material class of a launch (== RTW_MATERIAL_CLASS_* of rtwin.h): which instantiation of gprimary_kernel / gshade_kernel it runs.
+//   GENERAL   the whole material machine: tree walk, evaluation stack, Blend's draw, fuzzy Reflective's double-precision transcendentals, texels
+//   FLAT      every material tree of the scene is ONE node, Diffuse or Checker, and no mesh has a valid texture: the leaf is evaluated directly, a hit's
+//             sampled colour is exactly (1, 1, 1) with alpha 1, nothing is emitted -- fields 1 and 2 of a level are never written or read
+//   FLAT_TEX  the same trees, some mesh textured: the texel sample and the transparent-texel branch stay
+#define RTW_MC_GENERAL 0
+#define RTW_MC_FLAT 1
+#define RTW_MC_FLAT_TEX 2
 struct GroupTuning : AuxFork {      // (the sky-only tiles run on aux_stream beside the rest of the group)
     size_t capacity = 0;
+    int material_class = RTW_MC_GENERAL;   // the caller asks for a flat class only where its instantiations exist: no analytic shape, no lens, no work counters
     const float* gamma_thr = nullptr;
     bool has_analytic = false;     // some shape is a sphere / plane / capsule / triangle
     bool carry = false;            // ... and one of them follows a textured mesh: hit records carry the mesh hit whose texel the hit keeps
@@ -73,6 +82,7 @@ struct GroupTuning : AuxFork {      // (the sky-only tiles run on aux_stream bes
                                              // ahead of the bounce rounds; false: gprimary_kernel's LENS instantiation walks the trees itself (option "lens_route")
     hipEvent_t* timing = nullptr;  // null, or 4 events: before the primary kernel, after it, after the bounce rounds, after resolve
 };
+int material_class_of_launch(int scene_class, bool stats, bool has_analytic, bool lens);      // the class launch_render_group instantiates its shade / primary kernels for
 int launch_render_group(const RtwSceneDev* sc, void* accum, void* argb, void* workspace, const RtwGroupParams& g, const GroupTuning& tune, bool stats, hipStream_t stream);
 // ---- first-hit feature buffers (rtw_feature_kernels.h): g holds the frame, the tile mapping and the busy / sky tile lists of a group launch (rp.preview and
 // rp.max_bounce are not read); geom / albedo: float4 per pixel, ids: int32 x 2 per pixel ----

@@ -409,8 +409,9 @@ __device__ __forceinline__ f3 analytic_normal(const RtwShapeDev& sh, f3 pos, int
 
 // ---- RMeshShape::TestRayIntersection (Src/MeshShape.cpp:280-332) ------------------------------------
 // The part of RMeshShape::TestRayIntersection after the tree query (Src/MeshShape.cpp:288-327): barycentrics,
-// fast-normalised smooth normal, texture sample.
-template <bool STATS>
+// fast-normalised smooth normal, texture sample.  MC (rtw_device.h): in a FLAT scene no mesh has a valid texture -- the material index, the uv
+// interpolation and the texel sample are compiled out and the sampled colour stays the reset value.
+template <bool STATS, int MC = RTW_MC_GENERAL>
 __device__ __forceinline__ void mesh_finish(const RtwSceneDev* __restrict__ sc, const RtwShapeDev& sh, const TravCtx& tc,
                                             f3 pos, float cur, int slot, Hit& out, int& tri_index, Counters& ct)
 {
@@ -434,6 +435,7 @@ __device__ __forceinline__ void mesh_finish(const RtwSceneDev* __restrict__ sc, 
     out.normal = normalized_fast((n0 * bu + n1 * bv) + n2 * bw);
     out.color = mk(1.0f, 1.0f, 1.0f);      // *OutResult = HitResult resets the sampled colour (Src/KdTree.cpp:176)
     out.alpha = 1.0f;
+    if constexpr (MC == RTW_MC_FLAT) return;
     const int mat = __float_as_int(s3.w);
     if (mat != -1 && mat < sh.n_textures && mat < RTW_DEV_MAX_TEXTURES && sh.textures[mat].valid) {
         const float tu = (s2.y * bu + s2.w * bv) + s3.y * bw;      // t0*u + t1*v + t2*w
@@ -445,11 +447,11 @@ __device__ __forceinline__ void mesh_finish(const RtwSceneDev* __restrict__ sc, 
 
 // A recorded hit (shape, position, distance, leaf slot or analytic part) -> the RayHitResult RayTrace shades.  Records are only
 // kept for scenes in which no analytic hit can inherit a texel (the host sends the others through the single kernel).
-template <bool STATS>
+template <bool STATS, int MC = RTW_MC_GENERAL>
 __device__ __forceinline__ void hit_finish(const RtwSceneDev* __restrict__ sc, const RtwShapeDev& sh, const TravCtx& tc,
                                            f3 pos, float cur, int slot, Hit& out, int& tri_index, Counters& ct)
 {
-    if (sh.kind == RTW_SHAPE_MESH) { mesh_finish<STATS>(sc, sh, tc, pos, cur, slot, out, tri_index, ct); return; }
+    if (sh.kind == RTW_SHAPE_MESH) { mesh_finish<STATS, MC>(sc, sh, tc, pos, cur, slot, out, tri_index, ct); return; }
     out.pos = pos; out.dist = cur; out.normal = analytic_normal(sh, pos, slot);
     out.color = mk(1.0f, 1.0f, 1.0f); out.alpha = 1.0f;
     tri_index = -1;
@@ -570,11 +572,13 @@ __device__ __forceinline__ bool checker_brighter(f3 p, float size)
     return r;
 }
 
+// MC (rtw_device.h): a flat class's leaf is a Diffuse or a Checker -- the switch sees nothing but types 0 and 1 and keeps that case alone
+template <int MC = RTW_MC_GENERAL>
 __device__ __forceinline__ Bounce leaf_bounce(const RtwSceneDev* __restrict__ sc, const RtwMaterialNode& n, const Ray& in, const Hit& h, Ray& out, PathRng& rng)
 {
     Bounce b; b.att = mk(0, 0, 0); b.em = mk(0, 0, 0);
     const f3 albedo = mk(n.r, n.g, n.b);
-    switch (n.type) {
+    switch (MC != RTW_MC_GENERAL ? (n.type & 1) : n.type) {
     case 0: case 1: {
         const float factor = (n.type == 1) ? (checker_brighter(h.pos, n.param) ? 1.0f : 0.5f) : 1.0f;
         const float rd = in.dist - h.dist;
@@ -625,9 +629,18 @@ __device__ __forceinline__ f3 leaf_preview(const RtwMaterialNode& n, const Hit& 
 #define RTW_EVAL_DEPTH 2
 // Combine nesting is limited to RTW_EVAL_DEPTH = 2 so that the evaluation stack is two named register
 // sets (no dynamically indexed private array, hence no scratch memory).
-template <bool PREVIEW>
+// MC (rtw_device.h): in the flat classes the tree is its node 0, a Diffuse or a Checker -- no walk, no stack, no draw of Blend's, and of
+// leaf_bounce only the case that can be met (the same expressions in the same order).
+template <bool PREVIEW, int MC = RTW_MC_GENERAL>
 __device__ __forceinline__ Bounce material_eval(const RtwSceneDev* __restrict__ sc, const RtwShapeDev& sh, const Ray& in, const Hit& h, Ray& out, PathRng& rng)
 {
+    if constexpr (MC != RTW_MC_GENERAL) {
+        const RtwMaterialNode n = sh.material[0];
+        Bounce res; res.em = mk(0, 0, 0);
+        if (PREVIEW) res.att = leaf_preview(n, h);
+        else res = leaf_bounce<MC>(sc, n, in, h, out, rng);
+        return res;
+    }
     int node0 = 0, node1 = 0, phase0 = 0, phase1 = 0;
     Bounce saved0, saved1;
     saved0.att = saved0.em = saved1.att = saved1.em = mk(0, 0, 0);
@@ -1433,6 +1446,13 @@ size_t group_workspace_bytes(size_t capacity, int max_bounce, bool carry, GroupL
     return l.total;
 }
 
+// The flat classes' kernels exist for STATS off (the work is GENERAL's, so are its counters), without analytic shapes and without a lens: every other
+// launch is GENERAL's whatever the scene's class -- and says so (rtw_last_pass_material_class).
+int material_class_of_launch(int scene_class, bool stats, bool has_analytic, bool lens)
+{
+    return (stats || has_analytic || lens) ? RTW_MC_GENERAL : scene_class;
+}
+
 int launch_render_group(const RtwSceneDev* sc, void* accum, void* argb, void* workspace, const RtwGroupParams& g, const GroupTuning& tune, bool stats, hipStream_t stream)
 {
     const RtwRenderParams& p = g.rp;
@@ -1468,6 +1488,7 @@ int launch_render_group(const RtwSceneDev* sc, void* accum, void* argb, void* wo
     if (g.n_busy > 0) {
         const long long live_paths = (long long)g.n_busy * 64 * p.sub_samples * g.n_passes;
         const bool camera_round = p.lens != 0 && tune.camera_round;
+        const bool flat_class = material_class_of_launch(tune.material_class, stats, tune.has_analytic, p.lens != 0) != RTW_MC_GENERAL;
         if (camera_round) {
             // a lens, the camera round: glens_kernel only makes the rays (a wave per job and pass); trace(0) finds their hits and shade(1) is the first
             // per-hit block, so every round below is one later than without a lens
@@ -1479,10 +1500,17 @@ int launch_render_group(const RtwSceneDev* sc, void* accum, void* argb, void* wo
             const int ppw = (g.primary_passes > 1 && g.primary_passes * p.sub_samples <= 4) ? g.primary_passes : 1;        // as the kernel reads it
             const long long waves = (long long)g.n_jobs * ((g.n_passes + ppw - 1) / ppw);
             const unsigned pgrid = (unsigned)((waves + 3) / 4);
-            with_flags(stats, tune.has_analytic, p.cam_general != 0, p.lens != 0, [&](auto ST, auto AN, auto CAM, auto LENS) {
-                constexpr bool lens = decltype(LENS)::value, cam = decltype(CAM)::value || lens;
-                launch(gprimary_kernel<decltype(ST)::value, decltype(AN)::value, cam, lens>, dim3(pgrid), dim3(256), 0, stream, sc, gb, g);
-            });
+            if (flat_class) {               // (no work counters, no analytic shape, no lens: see material_class_of_launch)
+                with_flags(p.cam_general != 0, tune.material_class == RTW_MC_FLAT_TEX, [&](auto CAM, auto TEX) {
+                    constexpr int mc = decltype(TEX)::value ? RTW_MC_FLAT_TEX : RTW_MC_FLAT;
+                    launch(gprimary_kernel<false, false, decltype(CAM)::value, false, mc>, dim3(pgrid), dim3(256), 0, stream, sc, gb, g);
+                });
+            } else {
+                with_flags(stats, tune.has_analytic, p.cam_general != 0, p.lens != 0, [&](auto ST, auto AN, auto CAM, auto LENS) {
+                    constexpr bool lens = decltype(LENS)::value, cam = decltype(CAM)::value || lens;
+                    launch(gprimary_kernel<decltype(ST)::value, decltype(AN)::value, cam, lens>, dim3(pgrid), dim3(256), 0, stream, sc, gb, g);
+                });
+            }
         }
         if (tune.timing) (void)hipEventRecord(tune.timing[1], stream);
         constexpr int NTV = 128;            // wave-per-ray launches: 128-thread blocks, a wave takes rays in turn
@@ -1534,9 +1562,16 @@ int launch_render_group(const RtwSceneDev* sc, void* accum, void* argb, void* wo
                     });
                 });
             }
-            with_flags(stats, tune.has_analytic, [&](auto ST, auto AN) {
-                launch(gshade_kernel<decltype(ST)::value, decltype(AN)::value>, dim3(sb_full), dim3(256), 0, stream, sc, gb, g, r);
-            });
+            if (flat_class) {
+                with_flags(tune.material_class == RTW_MC_FLAT_TEX, [&](auto TEX) {
+                    constexpr int mc = decltype(TEX)::value ? RTW_MC_FLAT_TEX : RTW_MC_FLAT;
+                    launch(gshade_kernel<false, false, mc>, dim3(sb_full), dim3(256), 0, stream, sc, gb, g, r);
+                });
+            } else {
+                with_flags(stats, tune.has_analytic, [&](auto ST, auto AN) {
+                    launch(gshade_kernel<decltype(ST)::value, decltype(AN)::value>, dim3(sb_full), dim3(256), 0, stream, sc, gb, g, r);
+                });
+            }
         }
         if (tune.timing) (void)hipEventRecord(tune.timing[2], stream);
         if (tune.resolve_after) (void)hipStreamWaitEvent(stream, tune.resolve_after, 0);      // a pixel's passes are added in pass order

@@ -106,7 +106,10 @@ __device__ __forceinline__ void block_push(uint32_t* __restrict__ list, uint32_t
 // RayTrace's per-hit block (Src/RayTracerScene.cpp:47-94) for one path whose segment has just been traced (r0 = hit position +
 // distance, r1 = shape, leaf slot or part, carry).  Returns true when the path goes on (ray, rng, depth, nlev updated, its level
 // pushed); false when it ends: L is its radiance, the levels folded back in the reference's association order.
-template <bool STATS, bool AN>
+// MC: the scene's material class (rtw_device.h).  The flat classes drop what their scenes cannot reach and nothing else: the draws, the level
+// words that are written, the fold's operations and their order are GENERAL's.  FLAT: a hit's colour is exactly (1, 1, 1), its alpha 1 and nothing
+// is emitted, so fields 1 and 2 of a level are neither written nor read and no level is a transparent one; FLAT_TEX: only field 2 is not.
+template <bool STATS, bool AN, int MC = RTW_MC_GENERAL>
 __device__ __forceinline__ bool group_shade_step(const RtwSceneDev* __restrict__ sc, const RtwRenderParams& p, const GroupBufs& gb, uint32_t slot,
                                                  Ray& ray, PathRng& rng, int& depth, int& nlev, float4 r0, float4 r1, float4 r2, f3& L, Counters& ct)
 {
@@ -126,7 +129,7 @@ __device__ __forceinline__ bool group_shade_step(const RtwSceneDev* __restrict__
         const RtwShapeDev& sh = sc->shapes[hs];
         Hit h; int tri_index;
         if (AN) {
-            hit_finish<STATS>(sc, sh, tc, mk(r0.x, r0.y, r0.z), r0.w, hslot, h, tri_index, ct);
+            hit_finish<STATS, MC>(sc, sh, tc, mk(r0.x, r0.y, r0.z), r0.w, hslot, h, tri_index, ct);
             // one RayHitResult serves all shapes of a query (Src/RayTracerScene.cpp:99-125): a sphere / plane / capsule-side / RTriangle hit keeps
             // the sampled colour and alpha an earlier mesh hit of the same query left there
             const int cs = __float_as_int(r1.z);
@@ -136,17 +139,18 @@ __device__ __forceinline__ bool group_shade_step(const RtwSceneDev* __restrict__
                 h.color = hc.color; h.alpha = hc.alpha;
             }
         } else {
-            mesh_finish<STATS>(sc, sh, tc, mk(r0.x, r0.y, r0.z), r0.w, hslot, h, tri_index, ct);
+            mesh_finish<STATS, MC>(sc, sh, tc, mk(r0.x, r0.y, r0.z), r0.w, hslot, h, tri_index, ct);
         }
         if (!sh.has_material) { L = mk(0, 0, 0); done = true; }
         else {
             Ray out = ray;
             if (p.preview) {
-                const Bounce pv = material_eval<true>(sc, sh, ray, h, out, rng);
+                const Bounce pv = material_eval<true, MC>(sc, sh, ray, h, out, rng);
                 L = mk(0, 0, 0) + pv.att * h.color; done = true;
             } else {
-                const Bounce b = material_eval<false>(sc, sh, ray, h, out, rng);
-                if (rng.random() <= h.alpha) {
+                const Bounce b = material_eval<false, MC>(sc, sh, ray, h, out, rng);
+                const float u_alpha = rng.random();      // drawn whatever alpha is; a draw is at most 1.0f, FLAT's constant alpha
+                if (MC == RTW_MC_FLAT || u_alpha <= h.alpha) {
                     if (all_nonzero(b.att)) {
 #if RTW_LEVEL_SKIP
                         const bool c1 = __float_as_uint(h.color.x) == 0x3F800000u && __float_as_uint(h.color.y) == 0x3F800000u && __float_as_uint(h.color.z) == 0x3F800000u;
@@ -176,10 +180,10 @@ __device__ __forceinline__ bool group_shade_step(const RtwSceneDev* __restrict__
     for (int kk = nlev - 1; kk >= 0; kk--) {
         const float4 a = lv.at(kk, 0);
         const int kind = __float_as_int(a.w);
-        if ((kind & 3) == 0) {
+        if (MC == RTW_MC_FLAT || (kind & 3) == 0) {
             float4 c = make_float4(1.0f, 1.0f, 1.0f, 0.0f), e = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (!(kind & 4)) c = lv.at(kk, 1);
-            if (!(kind & 8)) e = lv.at(kk, 2);
+            if (MC != RTW_MC_FLAT && !(kind & 4)) c = lv.at(kk, 1);
+            if (MC == RTW_MC_GENERAL && !(kind & 8)) e = lv.at(kk, 2);
             L = (mk(0, 0, 0) + (mk(a.x, a.y, a.z) * L) * mk(c.x, c.y, c.z)) + mk(e.x, e.y, e.z);
         } else {
             L = mk(0, 0, 0) + L;
@@ -329,11 +333,14 @@ __device__ __forceinline__ void bins_walk_rays(const RtwShapeDev& sh, const uint
 
 __device__ __forceinline__ float pick4(int r, float a, float b, float c, float d) { return r == 0 ? a : (r == 1 ? b : (r == 2 ? c : d)); }
 
-template <bool STATS, bool AN, bool CAM, bool LENS = false>
+#ifndef RTW_GPRIMARY_FLAT_MINB
+#define RTW_GPRIMARY_FLAT_MINB 4 // the flat classes' instantiations: 112-114 VGPRs without a launch bound, no scratch (profiles/material_variants.md)
+#endif
+template <bool STATS, bool AN, bool CAM, bool LENS = false, int MC = RTW_MC_GENERAL>
 #ifndef RTW_GPRIMARY_MINB
 #define RTW_GPRIMARY_MINB 3      // measured in one session: 3 blocks of 256 per CU (<= 168 VGPRs) makes the primary kernel 13 % faster on unitychan (C4 0.343 -> 0.315 ms per pass), neutral on TorusKnot; 4 blocks (round 3, 128 VGPRs): C2 +3 %, C3 +4 % slower
 #endif
-__global__ __launch_bounds__(256, RTW_GPRIMARY_MINB) void gprimary_kernel(const RtwSceneDev* __restrict__ sc, GroupBufs gb, RtwGroupParams g)
+__global__ __launch_bounds__(256, MC == RTW_MC_GENERAL ? RTW_GPRIMARY_MINB : RTW_GPRIMARY_FLAT_MINB) void gprimary_kernel(const RtwSceneDev* __restrict__ sc, GroupBufs gb, RtwGroupParams g)
 {
     const RtwRenderParams& p = g.rp;
     const int npix = p.width * p.height;
@@ -528,7 +535,7 @@ __global__ __launch_bounds__(256, RTW_GPRIMARY_MINB) void gprimary_kernel(const 
             if (have_hit) {                                      // shade the hit here: the path's slot needs no queue position
                 Ray rs = ray; PathRng rg = rng; int depth = p.max_bounce, nlev = 0;
                 f3 L;
-                if (group_shade_step<STATS, AN>(sc, p, gb, slot, rs, rg, depth, nlev, hr0, hr1, hr2, L, ct)) {
+                if (group_shade_step<STATS, AN, MC>(sc, p, gb, slot, rs, rg, depth, nlev, hr0, hr1, hr2, L, ct)) {
                     group_save_state(gb, slot, rs, rg, depth, nlev, pixel, (kpass << 2) | (uint32_t)i);
                     queued |= 1u << r;
                     if (AN && p.lead_shapes > 0) {
@@ -1173,11 +1180,14 @@ __global__ __launch_bounds__(NT) void gtrace_wave_kernel(const RtwSceneDev* __re
 }
 
 // ---- shading of one round's hits: a path per lane ---------------------------------------------------------------------------------
-template <bool STATS, bool AN>
+#ifndef RTW_GSHADE_FLAT_MINB
+#define RTW_GSHADE_FLAT_MINB 8   // the flat classes' instantiations: 64 VGPRs or fewer without scratch (profiles/material_variants.md)
+#endif
+template <bool STATS, bool AN, int MC = RTW_MC_GENERAL>
 #ifndef RTW_GSHADE_MINB
 #define RTW_GSHADE_MINB 3
 #endif
-__global__ __launch_bounds__(256, RTW_GSHADE_MINB) void gshade_kernel(const RtwSceneDev* __restrict__ sc, GroupBufs gb, RtwGroupParams g, int round)
+__global__ __launch_bounds__(256, MC == RTW_MC_GENERAL ? RTW_GSHADE_MINB : RTW_GSHADE_FLAT_MINB) void gshade_kernel(const RtwSceneDev* __restrict__ sc, GroupBufs gb, RtwGroupParams g, int round)
 {
     // round >= 1: the paths of list (round - 1) have had their segment traced; the ones that go on join list `round`
     const RtwRenderParams& p = g.rp;
@@ -1210,7 +1220,7 @@ __global__ __launch_bounds__(256, RTW_GSHADE_MINB) void gshade_kernel(const RtwS
             float4 r2 = make_float4(0.f, 0.f, 0.f, 0.f);
             if (AN && gb.carry_on) r2 = gb.carry[slot];
             f3 L;
-            go_on = group_shade_step<STATS, AN>(sc, p, gb, slot, ray, rng, depth, nlev, r0, r1, r2, L, ct);
+            go_on = group_shade_step<STATS, AN, MC>(sc, p, gb, slot, ray, rng, depth, nlev, r0, r1, r2, L, ct);
             if (go_on) {
                 group_save_state(gb, slot, ray, rng, depth, nlev, pixel, pass_sub);
                 if (AN && p.lead_shapes > 0) {

@@ -144,6 +144,8 @@ struct rtw_context {
     int wave_below = 80000;             // a trace round with fewer rays (x 5 for trees of more than 4096 nodes) runs a wave per ray (measured with groups as two halves: C2 -3 % against 160 000; big trees keep 400 000)
     int device_build = 1;               // rtw_scene_commit builds the tree (KdNode::Build's decisions) and the layouts derived from it on the device (0: on the host)
     int last_pipeline = -1;             // the pipeline the latest render call actually ran (rtw_last_pass_pipeline)
+    int material_variants = 1;          // option: pipeline 4's shade / primary kernels by the scene's material class (rtw_device.h); 0: GENERAL's for every scene.  Same bits either way
+    int last_material_class = -1;       // the class the latest pipeline-4 call's shade / primary launches were instantiated for (rtw_last_pass_material_class)
     size_t workspace_limit = (size_t)24 << 30;  // a group's workspace may not exceed this (option "workspace_limit_mb"); hipMalloc failing counts as exceeding it
     int fallbacks = 0;                  // how many times a group was re-formed smaller after a refusal (rtw_context_memory_bytes' caller can see it: option-free diagnostics)
     // ray queries on device buffers (rtw_trace_closest_device / rtw_trace_occluded_device)
@@ -183,6 +185,9 @@ struct rtw_scene {
         int staged_tris = 0;            // ... and its triangles
         size_t last_nodes = 0;          // tree nodes of the last shape (the mesh of the two one-mesh forms above)
         bool big_tree = false;          // some tree has more than 4 096 nodes
+        bool flat = false;              // every shape that has a material has a tree of exactly ONE node, a Diffuse or a Checker
+        bool textured = false;          // some mesh has at least one valid texture entry
+        int material_class() const { return !flat ? RTW_MC_GENERAL : (textured ? RTW_MC_FLAT_TEX : RTW_MC_FLAT); }       // rtw_device.h
     } facts;
     int prune = 1;
     int traversal = 1;
@@ -383,6 +388,7 @@ int rtw_context_set_option(rtw_context* ctx, const char* name, int value)
     if (std::strcmp(name, "variance_prefilter") == 0) { ctx->variance_prefilter = value < 0 ? -1 : (value ? 1 : 0); return RTW_OK; }
     if (std::strcmp(name, "reproject_staging") == 0) { ctx->reproject_staging = value < 0 ? -1 : (value ? 1 : 0); return RTW_OK; }
     if (std::strcmp(name, "upsample_staging") == 0) { ctx->upsample_staging = value < 0 ? -1 : (value ? 1 : 0); return RTW_OK; }
+    if (std::strcmp(name, "material_variants") == 0) { ctx->material_variants = value ? 1 : 0; return RTW_OK; }
     if (std::strcmp(name, "lens_route") == 0) { ctx->lens_route = value < 0 ? -1 : (value ? 1 : 0); return RTW_OK; }
     if (std::strcmp(name, "query_blocks") == 0) { ctx->query_blocks = value < 0 ? 0 : value; return RTW_OK; }
     if (std::strcmp(name, "hint_period") == 0) { ctx->hint_period = value < 1 ? 1 : value; return RTW_OK; }
@@ -413,6 +419,12 @@ int rtw_last_pass_pipeline(rtw_context* ctx)
 {
     if (!ctx) return fail(RTW_ERR_INVALID, "context is null");
     return ctx->last_pipeline;
+}
+
+int rtw_last_pass_material_class(rtw_context* ctx)
+{
+    if (!ctx) return fail(RTW_ERR_INVALID, "context is null");
+    return ctx->last_material_class;
 }
 
 int rtw_context_synchronize(rtw_context* ctx)
@@ -920,6 +932,13 @@ int rtw_scene_commit(rtw_scene* scene)
             }
         f.last_nodes = n > 0 ? ms.back()->nodes.size() : 0;
         for (const auto& m : ms) if (m->nodes.size() > 4096) f.big_tree = true;
+        // the material class (rtw_device.h), from the trees and texture tables as uploaded above
+        f.flat = true;
+        for (const auto& m : ms) {
+            // (a shape without a material ends its paths in black: rare enough to stay with GENERAL)
+            if (!(m->material.size() == 1 &&(m->material[0].type == RTW_MAT_DIFFUSE || m->material[0].type == RTW_MAT_DIFFUSE_CHECKER))) f.flat = false;
+            for (size_t t = 0; t < m->textures.size() && t < RTW_DEV_MAX_TEXTURES; t++) if (m->kind == RTW_SHAPE_MESH && m->textures[t].valid) f.textured = true;
+        }
         scene->facts = f;
     }
     scene->allocs_at_commit = scene->allocs.size();
@@ -1701,6 +1720,7 @@ static int render_group(rtw_scene* scene, rtw_framebuffer* fb, const GroupReques
     set_aux_fork(cx, q.pos, &tune);
     tune.gamma_thr = cx->d_gamma;
     tune.has_analytic = scene->has_analytic; tune.carry = carry;
+    tune.material_class = cx->material_variants ? facts.material_class() : RTW_MC_GENERAL;
     tune.counters_clean = cx->group_clean[q.part];
     if (q.parts > 1) {       // a part of a split group: no sky tiles (the group's sky kernel was enqueued ahead of the parts, see rtw_render_passes); its resolve kernel after the previous part's
         tune.sky_passes = q.sky_passes; tune.sky_first_pass = q.sky_first;
@@ -1752,6 +1772,7 @@ static int render_group(rtw_scene* scene, rtw_framebuffer* fb, const GroupReques
     if (sky_only) return RTW_OK;
     clean = true;
     cx->last_pipeline = 4;
+    cx->last_material_class = rtw::material_class_of_launch(tune.material_class, cx->stats_enabled != 0, tune.has_analytic, p.lens != 0);
     cx->last_group_passes = q.parts > 1 ? q.sky_passes : n_passes;
     if (q.part == 0 && !cx->gcounters_pending && g.n_busy > 0 && (!(cx->known_gkey == key) || (cx->hint_tick++ % cx->hint_period) == 0)) {
         if (hipMemcpyAsync(cx->h_gcounters, (char*)cx->d_group_ws[0] + 256, 256, hipMemcpyDeviceToHost, cx->stream) == hipSuccess &&
