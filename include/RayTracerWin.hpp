@@ -307,6 +307,14 @@ inline void Upsample(ColorBuffer& Low, FeatureBuffers& LowFeatures, FeatureBuffe
 {
     RtwCheck(rtw_upsample(Low.Get(), LowFeatures.Get(), Features.Get(), &Params, Destination.Get()));
 }
+// rtw_sample_budget: how many more passes each pixel of Source needs, from its pass count and its luminance moments (dilated by Params.radius), into
+// BudgetDev: width x height int32 of device memory, what RayTracerScene::RenderPassesBudget reads.  Asynchronous, one launch.
+typedef rtw_sample_budget_params SampleBudgetParams;
+inline SampleBudgetParams SampleBudgetDefaults() { SampleBudgetParams p; RtwCheck(rtw_sample_budget_default_params(&p)); return p; }
+inline void SampleBudget(ColorBuffer& Source, Moments& Mom, void* BudgetDev, const SampleBudgetParams& Params = SampleBudgetDefaults())
+{
+    RtwCheck(rtw_sample_budget(Source.Get(), Mom.Get(), &Params, BudgetDev));
+}
 
 // ---- Src/RayTracerScene.h --------------------------------------------------------------------------------------------------------
 class RayTracerScene {
@@ -383,6 +391,15 @@ public:
     {
         Commit();
         RtwCheck(rtw_render_features(Scene, Buffers.Get(), TaskRows, Rank, World, FirstPass, Passes, SubSamples, Seed));
+    }
+    // Passes FirstPass .. FirstPass + Passes - 1 with a pass count per pixel: pixel p receives its first min(max(budget[p], 0), Passes) passes and ends
+    // with exactly the bits that many uniform passes leave in it; a pixel that receives none is not written.  BudgetDev: width x height int32 of device
+    // memory, row-major, written on the device's stream (SampleBudget does).  Asynchronous: rtw_render_passes_budget
+    void RenderPassesBudget(ColorBuffer& Buffer, const void* BudgetDev, int MaxBounceCount, int FirstPass, int Passes, int SubSamples = 4,
+                            uint32_t Seed = 12345, int TaskRows = 10, int Rank = 0, int World = 1)
+    {
+        Commit();
+        RtwCheck(rtw_render_passes_budget(Scene, Buffer.Get(), BudgetDev, TaskRows, Rank, World, MaxBounceCount, FirstPass, Passes, SubSamples, Seed));
     }
     void Commit() { if (!Committed) { RtwCheck(rtw_scene_commit(Scene)); Committed = true; } }
     rtw_scene* Get() { Commit(); return Scene; }

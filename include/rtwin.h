@@ -314,6 +314,20 @@ int rtw_render_tasks(rtw_scene* scene, rtw_framebuffer* fb, int task_rows, int r
 int rtw_render_passes(rtw_scene* scene, rtw_framebuffer* fb, int task_rows, int rank, int world,
                       int max_bounce, int use_base_color, int first_pass, int n_passes,
                       int sub_samples, uint32_t seed);
+/* Per-pixel pass budgets (adaptive sampling; no reference counterpart): rtw_render_passes with a pass count of each pixel's own.  budget_dev: width x
+ * height int32 in device memory, index py * width + px, read asynchronously on the context's streams (the caller orders its writes on the context's
+ * stream, as for rtw_trace_*_device).  With e(p) = min(max(budget[p], 0), n_passes), pixel p of this rank's tasks receives the passes
+ * first_pass .. first_pass + e(p) - 1 and nothing else: afterwards its accumulator entry and its ARGB word are, bit for bit, what
+ * rtw_render_passes(.., use_base_color = 0, first_pass, e(p), ..) leaves in that pixel from the same starting framebuffer (a pixel's pass is keyed by
+ * seed, pixel, pass and sub-sample alone, and every pixel carries its own pass count).  A pixel with e(p) == 0, or of another rank, is not written.
+ * Pipeline 4 only; groups, split groups, workspace and the fallback to smaller groups are those of rtw_render_passes with the same n_passes
+ * (rtw_render_reserve with the same arguments covers the call); paths that are not started leave their workspace slots unused, nothing is compacted and
+ * the host never waits to learn a count.  With a lens the camera rays take route 0 whatever "lens_route" says.  There is no preview mode.
+ * rtw_last_pass_pipeline, rtw_last_group_passes and rtw_last_pass_material_class report as for rtw_render_passes.
+ * RTW_ERR_INVALID, nothing launched: budget_dev null, a bad pass range, option "pipeline" 3 or 0 (or a scene on traversal 0), work counters enabled
+ * (rtw_stats_enable); every other error is rtw_render_passes', the 2^29 limit under a lens included. */
+int rtw_render_passes_budget(rtw_scene* scene, rtw_framebuffer* fb, const void* budget_dev, int task_rows, int rank, int world,
+                             int max_bounce, int first_pass, int n_passes, int sub_samples, uint32_t seed);
 
 /* Prepare, without rendering, everything a later rtw_render_passes call with these arguments would otherwise make inside it: the screen bins and tile
  * tables of this frame shape and the workspace of the largest group of passes that call will form (the workspace is grow-only; growing it waits for the
@@ -532,6 +546,25 @@ typedef struct rtw_upsample_params { float sigma_normal, sigma_depth; uint32_t f
 /* sigma_normal 0.3, sigma_depth 0.1 (they mean what they mean in rtw_denoise), both flags */
 int rtw_upsample_default_params(rtw_upsample_params* p);
 int rtw_upsample(rtw_framebuffer* lo, rtw_features* f_lo, rtw_features* f_hi, const rtw_upsample_params* p, rtw_framebuffer* dst);
+
+/* ---- luminance moments to per-pixel pass budgets: what rtw_render_passes_budget reads (no reference counterpart) ----
+ * How many MORE passes each pixel of src should get so that the standard error of its mean luminance falls to `tolerance` of that mean.  It takes buffers
+ * and no scene.  N = src.accum's count of the pixel, (mu1, mu2) = m's running means of its luminance and of the square (rtw_reproject_moments).  Every
+ * operation is float32 and rounded on its own (no contraction, correctly rounded division); max(a, 0) is fmaxf, so a NaN gives 0.
+ *     N < min_history                        b0 = max_passes                        (too short a history to trust the moments)
+ *     otherwise                              V = max(mu2 - mu1 * mu1, 0);  d = tolerance * (mu1 + 1e-3f);  need = V / (d * d);  x = need - (float)N
+ *         not (x < (float)max_passes)        b0 = max_passes                        (NaN comes here)
+ *         else x <= (float)min_passes        b0 = min_passes
+ *         else                               b0 = (int)ceilf(x)
+ *     budget[p] = the largest b0 among the pixels of the (2 radius + 1)^2 window around p that lie inside the frame   (an edge's neighbours are not starved)
+ * src and m are not written.  Asynchronous on the context's stream: ONE launch, no work space, no allocation, copy or synchronisation; budget_dev holds
+ * width x height int32, index py * width + px, device memory of the same device.
+ * RTW_ERR_INVALID, with budget_dev untouched: a null handle, params or pointer; src and m of different sizes or contexts; tolerance NaN or <= 0;
+ * min_passes < 0, max_passes < min_passes or max_passes > 65535; min_history < 1; radius outside 0..2. */
+typedef struct rtw_sample_budget_params { float tolerance; int min_history, min_passes, max_passes, radius; } rtw_sample_budget_params;
+/* tolerance 0.05, min_history 4, min_passes 0, max_passes 64, radius 1 */
+int rtw_sample_budget_default_params(rtw_sample_budget_params* p);
+int rtw_sample_budget(rtw_framebuffer* src, rtw_moments* m, const rtw_sample_budget_params* p, void* budget_dev);
 
 /* Device memory the context holds: workspaces + its share of the 201 MB unit-vector table (one copy per device, shared by the contexts on it).
  * The workspace is sized by the largest group of passes rendered (or reserved) so far: per path slot 116 B + 48 B x max_bounce, slots = pixels of the

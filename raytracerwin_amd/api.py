@@ -610,6 +610,36 @@ def reproject_moments(cam_cur, cam_prev, cur, f_cur, hist, f_hist, m_hist, dst, 
     _check(library().rtw_reproject_moments(cam(cam_cur), cam(cam_prev), cur.h, f_cur.h, hist.h, f_hist.h, m_hist.h, C.byref(params), int(moments_history), dst.h, m_dst.h))
 
 
+def _budget_pointer(budget, fb, who):
+    """the device pointer of a per-pixel budget: a contiguous int32 CUDA tensor with one value per pixel of fb, on the context's device"""
+    import torch
+    if not (isinstance(budget, torch.Tensor) and budget.is_cuda and budget.is_contiguous() and budget.dtype == torch.int32
+            and budget.numel() == fb.width * fb.height):
+        raise ValueError("%s: budget must be a contiguous int32 CUDA tensor with width * height elements" % who)
+    if budget.device.index != fb.ctx.device:
+        raise ValueError("%s: the budget must live on the context's device %d" % (who, fb.ctx.device))
+    return C.c_void_p(budget.data_ptr())
+
+
+class SampleBudgetParams(C.Structure):
+    """rtw_sample_budget_params; SampleBudgetParams() holds rtw_sample_budget_default_params' values (0.05, 4, 0, 64, 1), keywords override them"""
+    _fields_ = [("tolerance", C.c_float), ("min_history", C.c_int), ("min_passes", C.c_int), ("max_passes", C.c_int), ("radius", C.c_int)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        _check(library().rtw_sample_budget_default_params(C.byref(self)))
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+def sample_budget(src, moments, budget, params=None):
+    """rtw_sample_budget: how many more passes each pixel of the Framebuffer src needs, from its pass count and its luminance Moments, dilated by
+    params.radius, written into the int32 CUDA tensor budget (the formula is include/rtwin.h's) -- what RayTracerScene.render_passes_budget reads.
+    The caller orders its own use of the tensor on the context's stream.  Asynchronous, one launch."""
+    params = params if params is not None else SampleBudgetParams()
+    _check(library().rtw_sample_budget(src.h, moments.h, C.byref(params), _budget_pointer(budget, src, "sample_budget")))
+
+
 class DenoiseVarianceParams(C.Structure):
     """rtw_denoise_variance_params; DenoiseVarianceParams() holds rtw_denoise_variance_default_params' values (5, 4.0, 0.3, 0.1, both flags, 4)"""
     _fields_ = [("levels", C.c_int), ("sigma_lum", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("flags", C.c_uint32), ("min_history", C.c_int)]
@@ -933,6 +963,14 @@ class RayTracerScene:
         _check(library().rtw_render_passes(self.h, fb.h, int(task_rows), int(rank), int(world), int(MaxBounceCount),
                                            int(opt.UseBaseColor), int(first_pass), int(n_passes), int(sub_samples),
                                            C.c_uint32(seed)))
+
+    def render_passes_budget(self, fb, budget, task_rows, rank, world, MaxBounceCount, first_pass=0, n_passes=1, sub_samples=4, seed=12345):
+        """rtw_render_passes_budget: render_passes with a pass count per pixel.  budget is an int32 CUDA tensor, one value per pixel (row-major); pixel p
+        receives its first min(max(budget[p], 0), n_passes) passes of the call and ends with exactly the bits that many uniform passes leave in it; a
+        pixel that receives none is not written.  The caller orders its writes of the tensor on the context's stream."""
+        self.commit()
+        _check(library().rtw_render_passes_budget(self.h, fb.h, _budget_pointer(budget, fb, "render_passes_budget"), int(task_rows), int(rank), int(world),
+                                                  int(MaxBounceCount), int(first_pass), int(n_passes), int(sub_samples), C.c_uint32(seed)))
 
     def render_features(self, fb, task_rows=10, rank=0, world=1, first_pass=0, n_passes=1, sub_samples=4, seed=12345):
         """rtw_render_features: the first-hit features of the passes first_pass .. first_pass + n_passes - 1 over this rank's tasks, accumulated

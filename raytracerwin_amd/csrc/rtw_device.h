@@ -140,6 +140,15 @@ struct UpsampleCall {
 };
 bool upsample_is_staged(int staging);
 int launch_upsample(const UpsampleCall& u, hipStream_t stream);
+// ---- luminance moments -> per-pixel pass budgets (rtw_budget_kernels.h): one launch on `stream`, no workspace ----
+struct SampleBudgetCall {
+    const void *accum, *moments;                // float4 (sum rgb, int count) and float2 (mu1, mu2) per pixel (never written)
+    void* budget;                               // int32 per pixel
+    int width, height;
+    float tolerance;
+    int min_history, min_passes, max_passes, radius;    // radius 0..2
+};
+int launch_sample_budget(const SampleBudgetCall& s, hipStream_t stream);
 // ---- the variance-guided a-trous filter (rtw_variance_kernels.h): the estimate (prepare included), then `levels` level launches -- each preceded by a
 // prefilter launch when prefilter_pass is set -- ping-ponging between the workspace's two images, the last one writing dst ----
 struct DenoiseVarianceCall {

@@ -1120,6 +1120,7 @@ __global__ __launch_bounds__(256, 3) void shade_kernel(const RtwSceneDev* __rest
 #include "rtw_reproject_kernels.h"
 #include "rtw_variance_kernels.h"
 #include "rtw_upsample_kernels.h"
+#include "rtw_budget_kernels.h"
 #include "rtw_query_kernels.h"
 #include "rtw_build_kernels.h"
 
@@ -1457,10 +1458,14 @@ int launch_render_group(const RtwSceneDev* sc, void* accum, void* argb, void* wo
 {
     const RtwRenderParams& p = g.rp;
     if (g.n_passes <= 0 || (g.n_busy <= 0 && g.n_sky <= 0)) return 0;
+    // per-pixel pass budgets: the BUDGET instantiations of the three kernels that touch the frame; they exist without work counters and without the camera
+    // round (rtw_render_passes_budget refuses the one and never asks for the other)
+    const bool budget = g.budget != nullptr;
+    if (budget && (stats || (p.lens != 0 && tune.camera_round) || p.preview)) return (int)hipErrorInvalidValue;
     auto launch_sky = [&](const RtwGroupParams& gs, hipStream_t ss) {
         int sgrid = (gs.n_sky + 3) / 4;
         if (sgrid > tune.cu_count * tune.sky_blocks) sgrid = tune.cu_count * tune.sky_blocks;
-        with_flags(p.cam_general != 0, [&](auto CAM) { launch(gsky_kernel<decltype(CAM)::value>, dim3(sgrid), dim3(256), 0, ss, tune.gamma_thr, (float4*)accum, (uint32_t*)argb, gs); });
+        with_flags(p.cam_general != 0, budget, [&](auto CAM, auto BU) { launch(gsky_kernel<decltype(CAM)::value, decltype(BU)::value>, dim3(sgrid), dim3(256), 0, ss, tune.gamma_thr, (float4*)accum, (uint32_t*)argb, gs); });
     };
     if (tune.sky_mode == 2) {       // only the sky tiles of a split group, all the group's passes
         if (g.n_sky > 0) {
@@ -1501,9 +1506,14 @@ int launch_render_group(const RtwSceneDev* sc, void* accum, void* argb, void* wo
             const long long waves = (long long)g.n_jobs * ((g.n_passes + ppw - 1) / ppw);
             const unsigned pgrid = (unsigned)((waves + 3) / 4);
             if (flat_class) {               // (no work counters, no analytic shape, no lens: see material_class_of_launch)
-                with_flags(p.cam_general != 0, tune.material_class == RTW_MC_FLAT_TEX, [&](auto CAM, auto TEX) {
+                with_flags(p.cam_general != 0, tune.material_class == RTW_MC_FLAT_TEX, budget, [&](auto CAM, auto TEX, auto BU) {
                     constexpr int mc = decltype(TEX)::value ? RTW_MC_FLAT_TEX : RTW_MC_FLAT;
-                    launch(gprimary_kernel<false, false, decltype(CAM)::value, false, mc>, dim3(pgrid), dim3(256), 0, stream, sc, gb, g);
+                    launch(gprimary_kernel<false, false, decltype(CAM)::value, false, mc, decltype(BU)::value>, dim3(pgrid), dim3(256), 0, stream, sc, gb, g);
+                });
+            } else if (budget) {            // (no work counters)
+                with_flags(tune.has_analytic, p.cam_general != 0, p.lens != 0, [&](auto AN, auto CAM, auto LENS) {
+                    constexpr bool lens = decltype(LENS)::value, cam = decltype(CAM)::value || lens;
+                    launch(gprimary_kernel<false, decltype(AN)::value, cam, lens, RTW_MC_GENERAL, true>, dim3(pgrid), dim3(256), 0, stream, sc, gb, g);
                 });
             } else {
                 with_flags(stats, tune.has_analytic, p.cam_general != 0, p.lens != 0, [&](auto ST, auto AN, auto CAM, auto LENS) {
@@ -1575,7 +1585,7 @@ int launch_render_group(const RtwSceneDev* sc, void* accum, void* argb, void* wo
         }
         if (tune.timing) (void)hipEventRecord(tune.timing[2], stream);
         if (tune.resolve_after) (void)hipStreamWaitEvent(stream, tune.resolve_after, 0);      // a pixel's passes are added in pass order
-        launch(gresolve_kernel, dim3((unsigned)((g.n_busy + 3) / 4)), dim3(256), 0, stream, sc, (float4*)accum, (uint32_t*)argb, gb, g);
+        with_flags(budget, [&](auto BU) { launch(gresolve_kernel<decltype(BU)::value>, dim3((unsigned)((g.n_busy + 3) / 4)), dim3(256), 0, stream, sc, (float4*)accum, (uint32_t*)argb, gb, g); });
         if (tune.resolve_done) (void)hipEventRecord(tune.resolve_done, stream);
     } else if (tune.timing) {
         (void)hipEventRecord(tune.timing[1], stream); (void)hipEventRecord(tune.timing[2], stream);
@@ -1732,6 +1742,21 @@ int launch_upsample(const UpsampleCall& u, hipStream_t stream)
     const dim3 grid((unsigned)((u.width + UP_TILE_W - 1) / UP_TILE_W), (unsigned)((u.height + UP_TILE_H - 1) / UP_TILE_H));
     if (upsample_is_staged(u.staging)) launch(upsample_kernel<true>, grid, dim3(256), 0, stream, b);
     else launch(upsample_kernel<false>, grid, dim3(256), 0, stream, b);
+    return (int)hipGetLastError();
+}
+
+// ---- luminance moments -> per-pixel pass budgets (rtw_budget_kernels.h) ----------------------------------------------------------------------
+int launch_sample_budget(const SampleBudgetCall& s, hipStream_t stream)
+{
+    BudgetBufs b;
+    b.accum = (const float4*)s.accum; b.moments = (const Mu2*)s.moments; b.budget = (int32_t*)s.budget;
+    b.width = s.width; b.height = s.height; b.tolerance = s.tolerance;
+    b.min_history = s.min_history; b.min_passes = s.min_passes; b.max_passes = s.max_passes;
+    if (s.width < 1 || s.height < 1 || s.radius < 0 || s.radius > SB_MAX_R) return (int)hipErrorInvalidValue;
+    const dim3 grid((unsigned)((s.width + SB_TILE_W - 1) / SB_TILE_W), (unsigned)((s.height + SB_TILE_H - 1) / SB_TILE_H));
+    if (s.radius == 0) launch(sample_budget_kernel<0>, grid, dim3(256), 0, stream, b);
+    else if (s.radius == 1) launch(sample_budget_kernel<1>, grid, dim3(256), 0, stream, b);
+    else launch(sample_budget_kernel<2>, grid, dim3(256), 0, stream, b);
     return (int)hipGetLastError();
 }
 

@@ -74,6 +74,16 @@ __device__ __forceinline__ bool group_xy(const RtwGroupParams& g, int wt, int la
     const int pixel = y * g.rp.width + x;
     return live && pixel >= g.range_begin && pixel <= g.range_end;
 }
+// The BUDGET instantiations (rtw_render_passes_budget): how many of this launch's passes the pixel takes -- its first clamp(budget - g0, 0, n_passes).
+// A pixel's pass k is keyed by (seed, pixel, pass, sub-sample) alone and its colours are added in pass order, so a pixel that stops after e passes holds
+// the bits e uniform passes leave in it, whatever its neighbours do.
+__device__ __forceinline__ int group_budget(const RtwGroupParams& g, int pixel)
+{
+    const int v = g.budget[pixel];
+    const int e = (v > 0 ? v : 0) - g.g0;                // (g0 >= 0: no overflow)
+    return e < 0 ? 0 : (e < g.n_passes ? e : g.n_passes);
+}
+__device__ __forceinline__ int group_wave_max(int v) { for (int o = 32; o > 0; o >>= 1) { const int w = __shfl_xor(v, o); v = w > v ? w : v; } return v; }
 
 // A list push by a whole BLOCK of NW waves (every thread calls it, the same number of times): one atomic per block instead of one per wave.
 // The lists of a round have one counter; ~20 000 waves pushing to it one atomic each measured 6 us per pass of the C2 primary kernel (a third
@@ -230,7 +240,8 @@ __device__ __forceinline__ void group_save_state(const GroupBufs& gb, uint32_t s
 }
 
 // ---- sky-only tiles: K passes per pixel with the accumulator entry in registers ----------------------------------------------
-template <bool CAM>
+// BUDGET: the pass loop runs to the lane's own count; a lane whose pixel takes no pass of this launch reads and writes nothing.
+template <bool CAM, bool BUDGET = false>
 __global__ __launch_bounds__(256) void gsky_kernel(const float* __restrict__ gamma_thr, float4* __restrict__ accum, uint32_t* __restrict__ argb, RtwGroupParams g)
 {
     __shared__ float thr[256];
@@ -245,12 +256,14 @@ __global__ __launch_bounds__(256) void gsky_kernel(const float* __restrict__ gam
         int px = 0, py = 0;
         if (!group_xy(g, wt, lane_id(), px, py)) continue;
         const int pixel = py * p.width + px;
+        const int np = BUDGET ? group_budget(g, pixel) : g.n_passes;
+        if (BUDGET && np == 0) continue;
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
         if (!p.preview) acc = accum[pixel];
         f3 sum = mk(acc.x, acc.y, acc.z);
         int n = __float_as_int(acc.w);
         f3 c = mk(0, 0, 0);
-        for (int k = 0; k < g.n_passes; k++) {
+        for (int k = 0; k < np; k++) {
             f3 csum = mk(0, 0, 0);
             for (int i = 0; i < p.sub_samples; i++) {
                 PathRng rng; rng_init(rng, p.seed, phase, (uint64_t)npix, (uint32_t)pixel, (uint32_t)(g.first_pass + k), (uint32_t)i);
@@ -336,7 +349,11 @@ __device__ __forceinline__ float pick4(int r, float a, float b, float c, float d
 #ifndef RTW_GPRIMARY_FLAT_MINB
 #define RTW_GPRIMARY_FLAT_MINB 4 // the flat classes' instantiations: 112-114 VGPRs without a launch bound, no scratch (profiles/material_variants.md)
 #endif
-template <bool STATS, bool AN, bool CAM, bool LENS = false, int MC = RTW_MC_GENERAL>
+// BUDGET (per-pixel pass budgets, RtwGroupParams::budget): the wave loads its 64 pixels' counts once, beside group_xy, and takes their maximum.  No ray
+// set of the wave live (max <= kbase): it is idle -- no bin lookup, no ray, only the block's reservation, to which it brings nothing.  Otherwise the ray-set loop
+// and the shared walk are bounded by the maximum, and a ray set is live in a lane when the lane's own count reaches it: a dead ray is inactive in the
+// shared walk, writes no slot and joins no list.  A live ray runs the uniform kernel's expressions in the uniform kernel's order.
+template <bool STATS, bool AN, bool CAM, bool LENS = false, int MC = RTW_MC_GENERAL, bool BUDGET = false>
 #ifndef RTW_GPRIMARY_MINB
 #define RTW_GPRIMARY_MINB 3      // measured in one session: 3 blocks of 256 per CU (<= 168 VGPRs) makes the primary kernel 13 % faster on unitychan (C4 0.343 -> 0.315 ms per pass), neutral on TorusKnot; 4 blocks (round 3, 128 VGPRs): C2 +3 %, C3 +4 % slower
 #endif
@@ -363,23 +380,28 @@ __global__ __launch_bounds__(256, MC == RTW_MC_GENERAL ? RTW_GPRIMARY_MINB : RTW
         const uint32_t b = job & 0xFFFFFFu;
         const int only_sample = (int)((job >> 24) & 15u) - 1;        // -1: this wave does every sub-sample of its tile
         const uint32_t nsub = only_sample >= 0 ? 1u : (uint32_t)p.sub_samples;
-        const int nr = (int)(nsub * npw);                             // ray sets of this wave: r = (pass - kbase) * nsub + (index of the sub-sample)
         const int wt = g.busy_tiles ? (int)cldu(g.busy_tiles, (int)b) : g.first_tile + (int)b;
         const int lane = lane_id();
         int px = 0, py = 0;
         const bool live = group_xy(g, wt, lane, px, py);
         if (!live) { px = 0; py = 0; }
         const int pixel = live ? py * p.width + px : 0;
+        // BUDGET: the lanes' counts (64 neighbouring words of the tile's rows) and their maximum; the wave's passes end there
+        const int e_g = BUDGET && live ? group_budget(g, pixel) : 0;
+        const uint32_t most = BUDGET ? (uint32_t)group_wave_max(e_g) : 0u;
+        const uint32_t npw_b = !BUDGET ? npw : (most <= kbase ? 0u : (most - kbase < npw ? most - kbase : npw));
+        const int nr = (int)(nsub * npw_b);                           // ray sets of this wave: r = (pass - kbase) * nsub + (index of the sub-sample)
+        const bool idle = BUDGET && nr == 0;                          // no ray set of this wave is live: nothing below reads or writes anything
         // the wave's bin: all its pixels lie in one tile of the screen's bin grid (tile rows never straddle a bin row); a tile with a
         // live lane starts inside the frame (its first lane has the tile's smallest x and y)
         int bin = 0;
-        if (__ballot(live) != 0ull) {
+        if (!idle && __ballot(live) != 0ull) {
             int tx = 0, ty = 0;
             (void)work_to_xy(p, wt * 64, tx, ty);
             bin = (ty >> (6 - p.tile_shift)) * p.tiles_per_row + (tx >> p.tile_shift);
         }
         bool near_wave = false;          // can any sample of this wave's pixels hit anything?
-        for (int k = 0; k < n_shapes; k++) {
+        for (int k = 0; k < (idle ? 0 : n_shapes); k++) {
             const uint32_t* __restrict__ boff = p.bins[k].off;
             near_wave = near_wave || boff == nullptr || cldu(boff, bin) != cldu(boff, bin + 1);
         }
@@ -399,9 +421,10 @@ __global__ __launch_bounds__(256, MC == RTW_MC_GENERAL ? RTW_GPRIMARY_MINB : RTW
                     PathRng rng; rng_init(rng, p.seed, phase, (uint64_t)npix, (uint32_t)pixel, (uint32_t)g.first_pass + kbase + po, i);
                     const Ray ray = camera_ray_xy<CAM>(p, px, py, (int)i, rng);
                     float t0, t1;
+                    const bool live_r = BUDGET ? live && (int)(kbase + po) < e_g : live;
                     w_d[r] = ray.d; w_cur[r] = ray.dist;
-                    w_act[r] = live && slab_exact(ray, sh.bmin[0], sh.bmin[1], sh.bmin[2], sh.bmax[0], sh.bmax[1], sh.bmax[2], t0, t1);
-                    all_tame = all_tame && (!live || ray_is_tame(ray));
+                    w_act[r] = live_r && slab_exact(ray, sh.bmin[0], sh.bmin[1], sh.bmin[2], sh.bmax[0], sh.bmax[1], sh.bmax[2], t0, t1);
+                    all_tame = all_tame && (!live_r || ray_is_tame(ray));
                 }
             }
             if (__ballot(!all_tame) == 0ull) {
@@ -414,19 +437,20 @@ __global__ __launch_bounds__(256, MC == RTW_MC_GENERAL ? RTW_GPRIMARY_MINB : RTW
             const uint32_t po = (uint32_t)r / nsub, kpass = kbase + po;
             const int i = only_sample >= 0 ? only_sample : (int)((uint32_t)r - po * nsub);
             const int pass = g.first_pass + (int)kpass;
+            const bool live_r = BUDGET ? live && (int)kpass < e_g : live;      // this lane's ray of the set
             PathRng rng; rng_init(rng, p.seed, phase, (uint64_t)npix, (uint32_t)pixel, (uint32_t)pass, (uint32_t)i);
             const Ray ray = camera_ray_xy<CAM, LENS>(p, px, py, i, rng, (uint32_t)pass);
-            if (STATS && live) ct.cams++;
+            if (STATS && live_r) ct.cams++;
             const uint32_t slot = group_slot(g, b, (uint32_t)lane, (uint32_t)i, kpass);
             f3 si = mk(0, 0, 0);
             bool have_hit = false;
             float4 hr0 = make_float4(0.f, 0.f, 0.f, 0.f), hr1 = hr0, hr2 = hr0;
             if (p.max_bounce != 0 && !near_wave && !STATS) {     // no leaf of any shape can be met from this tile: every sample sees the sky
-                if (live) si = sky_color(ray.d.y);
+                if (live_r) si = sky_color(ray.d.y);
             } else if (shared_walk) {                            // the walk above found this ray's closest hit
-                if (STATS && live) { ct.rays++; ct.boxes++; }
+                if (STATS && live_r) { ct.rays++; ct.boxes++; }
                 const bool any = r == 0 ? w_any[0] : (r == 1 ? w_any[1] : (r == 2 ? w_any[2] : w_any[3]));
-                if (live) {
+                if (live_r) {
                     if (!any) si = sky_color(ray.d.y);
                     else {
                         have_hit = true;
@@ -442,17 +466,17 @@ __global__ __launch_bounds__(256, MC == RTW_MC_GENERAL ? RTW_GPRIMARY_MINB : RTW
                 int hit_shape = -1, hit_slot = -1, carry_shape = -1, carry_slot = -1;
                 f3 hit_pos = mk(0, 0, 0), carry_pos = mk(0, 0, 0);
                 float seg = ray.dist, carry_dist = 0.0f;
-                if (STATS && live) ct.rays++;
+                if (STATS && live_r) ct.rays++;
                 const bool tame = ray_is_tame(ray);
-                const bool any_untame = __ballot(live && !tame) != 0ull;
+                const bool any_untame = __ballot(live_r && !tame) != 0ull;
                 const bool skx = near_zero(ray.d.x), sky = near_zero(ray.d.y), skz = near_zero(ray.d.z);
                 for (int k = 0; k < n_shapes; k++) {
                     const RtwShapeDev& sh = sc->shapes[k];
                     const int kind = AN ? sh.kind : RTW_SHAPE_MESH;
                     float t0, t1;
-                    const bool inbox = live && ((AN && kind == RTW_SHAPE_PLANE) ||      // a plane has no culling box (RPlane::HasCullingBounds)
+                    const bool inbox = live_r && ((AN && kind == RTW_SHAPE_PLANE) ||      // a plane has no culling box (RPlane::HasCullingBounds)
                                                 slab_exact(ray, sh.bmin[0], sh.bmin[1], sh.bmin[2], sh.bmax[0], sh.bmax[1], sh.bmax[2], t0, t1));
-                    if (STATS && live && kind != RTW_SHAPE_PLANE) ct.boxes++;
+                    if (STATS && live_r && kind != RTW_SHAPE_PLANE) ct.boxes++;
                     if (__ballot(inbox) == 0ull) continue;
                     float cur = seg; f3 pos = mk(0, 0, 0); int slot_hit = -1;
                     bool any = false;
@@ -522,7 +546,7 @@ __global__ __launch_bounds__(256, MC == RTW_MC_GENERAL ? RTW_GPRIMARY_MINB : RTW
                         else if (AN && slot_hit != 0) carry_shape = -1;      // a capsule end resets the sampled colour (Src/Shapes.cpp:34-62)
                     }
                 }
-                if (live) {
+                if (live_r) {
                     if (hit_shape < 0) si = sky_color(ray.d.y);
                     else {
                         have_hit = true;
@@ -547,7 +571,7 @@ __global__ __launch_bounds__(256, MC == RTW_MC_GENERAL ? RTW_GPRIMARY_MINB : RTW
                     si = mk(0, 0, 0) + L;
                     gb.rad[slot] = make_float4(si.x, si.y, si.z, 0.0f);
                 }
-            } else if (live) {
+            } else if (live_r) {
                 gb.rad[slot] = make_float4(si.x, si.y, si.z, 0.0f);
             }
         }
@@ -1237,6 +1261,8 @@ __global__ __launch_bounds__(256, MC == RTW_MC_GENERAL ? RTW_GSHADE_MINB : RTW_G
 }
 
 // ---- the group's pixels of the busy tiles: accumulate + resolve, pass by pass ---------------------------------------------------
+// BUDGET: a pixel adds the passes it took (the slots of the others were never written) and is not stored when it took none.
+template <bool BUDGET = false>
 __global__ __launch_bounds__(256) void gresolve_kernel(const RtwSceneDev* __restrict__ sc, float4* __restrict__ accum, uint32_t* __restrict__ argb,
                                                        GroupBufs gb, RtwGroupParams g)
 {
@@ -1249,14 +1275,16 @@ __global__ __launch_bounds__(256) void gresolve_kernel(const RtwSceneDev* __rest
     if (b < (uint32_t)g.n_busy) {
         const int wt = g.busy_tiles ? (int)g.busy_tiles[b] : g.first_tile + (int)b;
         int px = 0, py = 0;
-        if (group_xy(g, wt, (int)lane, px, py)) {
+        const bool live = group_xy(g, wt, (int)lane, px, py);
+        const int np = !BUDGET ? g.n_passes : (live ? group_budget(g, py * p.width + px) : 0);
+        if (live && !(BUDGET && np == 0)) {
             const int pixel = py * p.width + px;
             float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
             if (!p.preview) acc = accum[pixel];
             f3 sum = mk(acc.x, acc.y, acc.z);
             int n = __float_as_int(acc.w);
             f3 c = mk(0, 0, 0);
-            for (int k = 0; k < g.n_passes; k++) {
+            for (int k = 0; k < np; k++) {
                 c = mk(0, 0, 0);
                 for (int i = 0; i < p.sub_samples; i++) {
                     const float4 r = gb.rad[group_slot(g, b, lane, (uint32_t)i, (uint32_t)k)];

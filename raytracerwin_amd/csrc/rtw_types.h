@@ -201,6 +201,10 @@ struct RtwGroupParams {
     int32_t range_begin, range_end; // inclusive pixel range that is rendered (a lane outside it is dead)
     int32_t first_tile;
     int32_t primary_passes;         // passes one wave of the primary kernel takes for its tile (> 1: x sub-samples <= 4; -1: one ray set at a time, no shared walk)
+    // per-pixel pass budgets (rtw_render_passes_budget; read by the kernels' BUDGET instantiations only): budget[py * width + px] passes of the CALL go to
+    // the pixel, this launch renders the call's passes g0 .. g0 + n_passes - 1, so the pixel takes the first clamp(budget - g0, 0, n_passes) of them
+    const int32_t* budget;          // null: every pixel takes every pass (the uniform kernels)
+    int32_t g0;
 };
 
 // random-stream constants (shared with the oracle by specification, not by code)

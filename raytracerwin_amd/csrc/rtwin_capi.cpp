@@ -1665,6 +1665,8 @@ struct GroupRequest {
     // tiles get all its passes (sky_first, sky_passes) from ONE launch enqueued ahead of the parts (sky_only), which touches no workspace
     int part = 0, parts = 1, sky_first = 0, sky_passes = 0; bool sky_only = false;
     RunPos pos = RUN_ALONE;
+    // per-pixel pass budgets (rtw_render_passes_budget): the call's budgets (null: a uniform launch) and where this launch's first pass stands in the call
+    const void* budget = nullptr; int g0 = 0;
 };
 
 
@@ -1687,6 +1689,7 @@ static int render_group(rtw_scene* scene, rtw_framebuffer* fb, const GroupReques
     RtwGroupParams g; std::memset(&g, 0, sizeof g);
     g.first_pass = first_pass; g.n_passes = n_passes;
     g.range_begin = range_begin; g.range_end = range_end; g.first_tile = 0;
+    g.budget = (const int32_t*)q.budget; g.g0 = q.g0;
     if (cx->stats_enabled) ranged = true;       // work counters: every camera ray goes through the primary kernel, which counts (the sky kernel does not)
     if (ranged) {           // every tile of the range is a job; the primary kernel finds out which see the sky only
         g.n_busy = p.count >> 6; g.n_sky = 0; g.n_jobs = g.n_busy;
@@ -1747,7 +1750,7 @@ static int render_group(rtw_scene* scene, rtw_framebuffer* fb, const GroupReques
     // (keyed by the launch shape WITHOUT the number of passes: the lengths are kept per pass and scaled to the group at hand, so a warm-up call of any
     // length primes a longer one)
     rtw_context::GroupKey key; key.scene = scene; key.capacity = (long long)((size_t)g.n_busy * 64 * (size_t)sub_samples); key.max_bounce = max_bounce; key.preview = p.preview; key.n_passes = 0;
-    const bool camera_round = p.lens != 0 && lens_uses_camera_round(cx);
+    const bool camera_round = p.lens != 0 && !q.budget && lens_uses_camera_round(cx);     // (a budgeted launch: route 0, the primary kernel's LENS instantiation)
     if (camera_round) key.n_passes = -2;       // (its lists are one round later: the lengths of the other kind of group say nothing)
     if (cx->gcounters_pending && hipEventQuery(cx->gcounters_event) == hipSuccess) {
         cx->known_gkey = cx->gcounters_key; cx->gcounters_pending = false;
@@ -1774,7 +1777,8 @@ static int render_group(rtw_scene* scene, rtw_framebuffer* fb, const GroupReques
     cx->last_pipeline = 4;
     cx->last_material_class = rtw::material_class_of_launch(tune.material_class, cx->stats_enabled != 0, tune.has_analytic, p.lens != 0);
     cx->last_group_passes = q.parts > 1 ? q.sky_passes : n_passes;
-    if (q.part == 0 && !cx->gcounters_pending && g.n_busy > 0 && (!(cx->known_gkey == key) || (cx->hint_tick++ % cx->hint_period) == 0)) {
+    // (a budgeted launch is sized by the uniform launches' list lengths, an upper bound of its own, and files none: its shorter lists would undersize them)
+    if (q.part == 0 && !q.budget && !cx->gcounters_pending && g.n_busy > 0 && (!(cx->known_gkey == key) || (cx->hint_tick++ % cx->hint_period) == 0)) {
         if (hipMemcpyAsync(cx->h_gcounters, (char*)cx->d_group_ws[0] + 256, 256, hipMemcpyDeviceToHost, cx->stream) == hipSuccess &&
             hipEventRecord(cx->gcounters_event, cx->stream) == hipSuccess) {
             cx->gcounters_pending = true; cx->gcounters_key = key; cx->gcounters_passes = n_passes;
@@ -1907,6 +1911,10 @@ int rtw_render_tasks(rtw_scene* scene, rtw_framebuffer* fb, int task_rows, int r
     return render_tasks(scene, fb, task_rows, rank, world, max_bounce, use_base_color, pass_index, sub_samples, seed, RUN_ALONE);
 }
 
+// The groups of one call through the pass-batched pipeline: rtw_render_passes (budget null) and rtw_render_passes_budget share them.
+static int render_pass_groups(rtw_scene* scene, rtw_framebuffer* fb, int task_rows, int rank, int world, int max_bounce, int use_base_color,
+                              int first_pass, int n_passes, int sub_samples, uint32_t seed, const void* budget);
+
 // n_passes accumulated passes (UpdateBitmapPixels' sample loop, Src/RayTracerProgram.cpp:317-361) over this rank's tasks.
 int rtw_render_passes(rtw_scene* scene, rtw_framebuffer* fb, int task_rows, int rank, int world, int max_bounce, int use_base_color,
                       int first_pass, int n_passes, int sub_samples, uint32_t seed)
@@ -1926,16 +1934,39 @@ int rtw_render_passes(rtw_scene* scene, rtw_framebuffer* fb, int task_rows, int 
         }
         return RTW_OK;
     }
+    return render_pass_groups(scene, fb, task_rows, rank, world, max_bounce, use_base_color, first_pass, n_passes, sub_samples, seed, nullptr);
+}
+
+// The same passes under per-pixel budgets (rtwin.h): the groups of the uniform call, every launch with the budgets and its offset into the call.
+int rtw_render_passes_budget(rtw_scene* scene, rtw_framebuffer* fb, const void* budget_dev, int task_rows, int rank, int world, int max_bounce,
+                             int first_pass, int n_passes, int sub_samples, uint32_t seed)
+{
+    int rc = need_committed(scene); if (rc != RTW_OK) return rc;
+    if (!fb) return fail(RTW_ERR_INVALID, "framebuffer is null");
+    if (!budget_dev) return fail(RTW_ERR_INVALID, "the budget is null");
+    if (n_passes < 0 || first_pass < 0) return fail(RTW_ERR_INVALID, "bad pass range");
+    if (!group_pipeline_ok(scene)) return fail(RTW_ERR_INVALID, "per-pixel budgets need the pass-batched pipeline (option \"pipeline\" 4, traversal != 0)");
+    if (scene->ctx->stats_enabled) return fail(RTW_ERR_INVALID, "per-pixel budgets do not run with work counters enabled");
+    if (scene->has_lens() && (long long)first_pass + n_passes > (1ll << 29)) return fail(RTW_ERR_LIMIT, "pass_index must stay below 2^29 with a lens");
+    return render_pass_groups(scene, fb, task_rows, rank, world, max_bounce, 0, first_pass, n_passes, sub_samples, seed, budget_dev);
+}
+
+static int render_pass_groups(rtw_scene* scene, rtw_framebuffer* fb, int task_rows, int rank, int world, int max_bounce, int use_base_color,
+                              int first_pass, int n_passes, int sub_samples, uint32_t seed, const void* budget)
+{
+    rtw_context* cx = scene->ctx;
+    int rc;
     // groups of passes share one set of launches (rtw_group_kernels.h); the groups of this call fork the second stream once and join it once
     GroupCall gc;
     rc = plan_group_call(scene, fb, task_rows, rank, world, max_bounce, first_pass, sub_samples, &gc); if (rc != RTW_OK) return rc;
     if (gc.p.count == 0) return RTW_OK;
     GroupRequest q = one_pass(gc.p, false, 0, fb->width * fb->height - 1, max_bounce, use_base_color, first_pass, sub_samples, seed);
+    q.budget = budget;
     GroupWalk w{cx, gc.per_pass, n_passes, max_bounce, scene->texture_carry, use_base_color != 0};
     while (w.next()) {
         bool refused = false;
         rc = RTW_OK;
-        q.first_pass = first_pass + w.done; q.n_passes = w.k; q.pos = run_pos(w.first(), w.last());
+        q.first_pass = first_pass + w.done; q.g0 = w.done; q.n_passes = w.k; q.pos = run_pos(w.first(), w.last());
         q.part = 0; q.parts = w.parts; q.sky_only = false;
         if (w.parts > 1) {
             // The group as `parts` parts on as many streams.  Its kernels are bound by latency, not by a throughput roof: every stage of a
@@ -1958,7 +1989,7 @@ int rtw_render_passes(rtw_scene* scene, rtw_framebuffer* fb, int task_rows, int 
                 for (int j = 0; j < w.parts && rc == RTW_OK; j++) {
                     q.part = j; q.n_passes = w.part_passes(j);
                     rc = render_group(scene, fb, q, &refused);
-                    q.first_pass += q.n_passes;
+                    q.first_pass += q.n_passes; q.g0 += q.n_passes;
                 }
                 for (int j = 1; j < w.parts; j++) {
                     (void)hipEventRecord(cx->part_done[j], cx->part_stream[j]);
@@ -2387,6 +2418,34 @@ int rtw_upsample(rtw_framebuffer* lo, rtw_features* f_lo, rtw_features* f_hi, co
     u.sigma_normal = p->sigma_normal; u.sigma_depth = p->sigma_depth; u.flags = p->flags; u.staging = cx->upsample_staging;
     const hipError_t e = (hipError_t)rtw::launch_upsample(u, cx->stream);
     if (e != hipSuccess) return hip_fail(e, "upsample launch");
+    return RTW_OK;
+}
+
+// ---- luminance moments to per-pixel pass budgets (rtw_budget_kernels.h; the formula is rtwin.h's) -----------------------------------------
+int rtw_sample_budget_default_params(rtw_sample_budget_params* p)
+{
+    if (!p) return fail(RTW_ERR_INVALID, "null");
+    p->tolerance = 0.05f; p->min_history = 4; p->min_passes = 0; p->max_passes = 64; p->radius = 1;
+    return RTW_OK;
+}
+
+int rtw_sample_budget(rtw_framebuffer* src, rtw_moments* m, const rtw_sample_budget_params* p, void* budget_dev)
+{
+    if (!src || !m || !p || !budget_dev) return fail(RTW_ERR_INVALID, "null argument");
+    if (src->ctx != m->ctx) return fail(RTW_ERR_INVALID, "source and moments belong to different contexts");
+    if (src->width != m->width || src->height != m->height) return fail(RTW_ERR_INVALID, "source and moments differ in size");
+    if (!(p->tolerance > 0.0f)) return fail(RTW_ERR_INVALID, "tolerance must be positive");
+    if (p->min_passes < 0 || p->max_passes < p->min_passes || p->max_passes > 65535) return fail(RTW_ERR_INVALID, "need 0 <= min_passes <= max_passes <= 65535");
+    if (p->min_history < 1) return fail(RTW_ERR_INVALID, "min_history must be >= 1");
+    if (p->radius < 0 || p->radius > 2) return fail(RTW_ERR_INVALID, "radius must be 0..2");
+    rtw_context* cx = src->ctx;
+    HIP_TRY(hipSetDevice(cx->device));
+    rtw::SampleBudgetCall s;
+    s.accum = src->accum; s.moments = m->mu; s.budget = budget_dev;
+    s.width = src->width; s.height = src->height; s.tolerance = p->tolerance;
+    s.min_history = p->min_history; s.min_passes = p->min_passes; s.max_passes = p->max_passes; s.radius = p->radius;
+    const hipError_t e = (hipError_t)rtw::launch_sample_budget(s, cx->stream);
+    if (e != hipSuccess) return hip_fail(e, "sample budget launch");
     return RTW_OK;
 }
 
