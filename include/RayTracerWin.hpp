@@ -315,6 +315,9 @@ inline void SampleBudget(ColorBuffer& Source, Moments& Mom, void* BudgetDev, con
 {
     RtwCheck(rtw_sample_budget(Source.Get(), Mom.Get(), &Params, BudgetDev));
 }
+// rtw_occlusion_params for RayTracerScene::RenderOcclusion: radius 1, bias 1e-3, 8 samples per pass, cosine-weighted
+typedef rtw_occlusion_params OcclusionParams;
+inline OcclusionParams OcclusionDefaults() { OcclusionParams p; RtwCheck(rtw_occlusion_default_params(&p)); return p; }
 
 // ---- Src/RayTracerScene.h --------------------------------------------------------------------------------------------------------
 class RayTracerScene {
@@ -400,6 +403,14 @@ public:
     {
         Commit();
         RtwCheck(rtw_render_passes_budget(Scene, Buffer.Get(), BudgetDev, TaskRows, Rank, World, MaxBounceCount, FirstPass, Passes, SubSamples, Seed));
+    }
+    // Ambient occlusion of what Features show, under the current camera: Params.samples rays of length Params.radius per pixel and pass into the
+    // hemisphere of the pixel's normal, the passes FirstPass .. FirstPass + Passes - 1 accumulated into Destination like render passes (so Denoise,
+    // Reproject, Upsample and SaveBufferToPNG take it as it is).  Asynchronous, one launch: rtw_render_occlusion
+    void RenderOcclusion(FeatureBuffers& Features, const OcclusionParams& Params, int FirstPass, int NumPasses, uint32_t Seed, ColorBuffer& Destination)
+    {
+        Commit();
+        RtwCheck(rtw_render_occlusion(Scene, Features.Get(), &Params, FirstPass, NumPasses, Seed, Destination.Get()));
     }
     void Commit() { if (!Committed) { RtwCheck(rtw_scene_commit(Scene)); Committed = true; } }
     rtw_scene* Get() { Commit(); return Scene; }

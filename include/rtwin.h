@@ -566,6 +566,37 @@ typedef struct rtw_sample_budget_params { float tolerance; int min_history, min_
 int rtw_sample_budget_default_params(rtw_sample_budget_params* p);
 int rtw_sample_budget(rtw_framebuffer* src, rtw_moments* m, const rtw_sample_budget_params* p, void* budget_dev);
 
+/* ---- ambient occlusion from the feature buffers: the tree walk's cheap consumer of a first hit (no reference counterpart) ----
+ * How open the surface a pixel shows is: `samples` short rays per pass from the pixel's first hit into the hemisphere of its normal, the share of them
+ * (cosine-weighted or not) that reach `radius` unoccluded.  The frame is W x H, shared by f and dst, in the scene's context; the camera is the scene's
+ * current camera.  Everything is float32, every product and every sum rounded on its own, in the order written.
+ *  1 empty pixels    cf = the int count in f.albedo.w.  A pixel with cf == 0 is EMPTY and is not written.
+ *  2 open pixels     z = geom.w / cf;  m = geom.xyz / cf per channel;  n = normalized(m) (tiny vectors are left as they are).  The pixel is OPEN when
+ *                    ids.shape < 0 or m.x * m.x + m.y * m.y + m.z * m.z is nearer to 0 than FLT_EPSILON.  An OPEN pixel casts no ray: a = 1 in every pass.
+ *  3 ray origin      P = the point the pinhole ray of pixel (x, y) reaches after the distance z (rtw_reproject's step 1: also under a lens);
+ *                    O = P + n * bias, per component P.c + n.c * bias.
+ *  4 sample rays     for pass k = first_pass .. first_pass + n_passes - 1 and sample s = 0 .. samples - 1:
+ *                    key = stream_key(seed, pixel, (k * 64 + s) | 0x40000000) with pixel = y * W + x;  idx = stream_draw31(key, 0) mod RTW_UNIT_TABLE_SIZE;
+ *                    v = rtw_unit_table_entry(idx) (no phase, no debug mask);  d = v when dot(v, n) > 0, else reflect(v, n) = v - (n * 2) * dot(v, n).
+ *                    The ray is (O, d, radius).  o_s = 1 when rtw_trace_occluded would report it occluded, else 0.
+ *                    c_s = max(0, dot(n, d)) with RTW_OCCLUSION_COSINE, else 1;  t_s = o_s ? 0 : c_s.
+ *  5 per-pass value  A = t_0 + t_1 + ..., Wt = c_0 + c_1 + ..., both summed left to right from +0;  a = Wt > 0 ? A / Wt : 1.
+ *  6 accumulation    per pass, in order: dst.accum.xyz += (a, a, a), count += 1 (AddPixel's shape).  After the call's last pass dst.argb is the gamma
+ *                    pack of accum.xyz / count.  Calls accumulate until rtw_framebuffer_clear; dst is an ordinary framebuffer for every other call.
+ * The result depends on the scene, the camera, f, the parameters, the passes and the seed only: no option of the context or of the scene changes a bit
+ * of it.  The context option "occlusion_order" (-1) picks how the rays are dealt to the lanes -- 0 = a lane per pixel, 1 = a lane per sample, -1 = the
+ * faster by measurement.  The whole frame is covered: a rank that rendered only its own feature rows processes only those, by rule 1.
+ * f is not written.  Asynchronous on the context's stream: ONE launch whatever n_passes is (the passes loop inside the kernel; a pixel's accumulator entry
+ * is read once and written once), no work space, no allocation, copy or synchronisation.  The work counters (rtw_stats) do not count these rays.
+ * RTW_ERR_STATE: the scene is not committed.  RTW_ERR_INVALID, with dst untouched: a null handle or params; f and dst of different sizes, or handles of
+ * different contexts; samples outside 1..64; radius NaN or <= 0; bias NaN or < 0; unknown flag bits; n_passes < 1; first_pass < 0 or
+ * first_pass + n_passes > 2^24. */
+#define RTW_OCCLUSION_COSINE 1u
+typedef struct rtw_occlusion_params { float radius, bias; int samples; uint32_t flags; } rtw_occlusion_params;
+/* radius 1.0, bias 1e-3, samples 8, flags RTW_OCCLUSION_COSINE */
+int rtw_occlusion_default_params(rtw_occlusion_params* p);
+int rtw_render_occlusion(rtw_scene* scene, rtw_features* f, const rtw_occlusion_params* p, int first_pass, int n_passes, uint32_t seed, rtw_framebuffer* dst);
+
 /* Device memory the context holds: workspaces + its share of the 201 MB unit-vector table (one copy per device, shared by the contexts on it).
  * The workspace is sized by the largest group of passes rendered (or reserved) so far: per path slot 116 B + 48 B x max_bounce, slots = pixels of the
  * frame's busy tiles x sub-samples x passes per group; e.g. TorusKnot 1080p depth 4: 21 MB for one pass per call,

@@ -640,6 +640,18 @@ def sample_budget(src, moments, budget, params=None):
     _check(library().rtw_sample_budget(src.h, moments.h, C.byref(params), _budget_pointer(budget, src, "sample_budget")))
 
 
+class OcclusionParams(C.Structure):
+    """rtw_occlusion_params; OcclusionParams() holds rtw_occlusion_default_params' values (1.0, 1e-3, 8, COSINE), keywords override them"""
+    _fields_ = [("radius", C.c_float), ("bias", C.c_float), ("samples", C.c_int), ("flags", C.c_uint32)]
+    COSINE = 1
+
+    def __init__(self, **kw):
+        super().__init__()
+        _check(library().rtw_occlusion_default_params(C.byref(self)))
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
 class DenoiseVarianceParams(C.Structure):
     """rtw_denoise_variance_params; DenoiseVarianceParams() holds rtw_denoise_variance_default_params' values (5, 4.0, 0.3, 0.1, both flags, 4)"""
     _fields_ = [("levels", C.c_int), ("sigma_lum", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("flags", C.c_uint32), ("min_history", C.c_int)]
@@ -978,6 +990,14 @@ class RayTracerScene:
         self.commit()
         _check(library().rtw_render_features(self.h, fb.h, int(task_rows), int(rank), int(world), int(first_pass), int(n_passes),
                                              int(sub_samples), C.c_uint32(seed)))
+
+    def render_occlusion(self, features, dst, params=None, first_pass=0, n_passes=1, seed=12345):
+        """rtw_render_occlusion: ambient occlusion of what the FeatureBuffers show under the current camera -- params.samples rays of length
+        params.radius per pixel and pass into the hemisphere of the pixel's normal -- the passes accumulated into the Framebuffer dst like render
+        passes (the formula is include/rtwin.h's).  Asynchronous on the context's stream, one launch."""
+        self.commit()
+        params = params if params is not None else OcclusionParams()
+        _check(library().rtw_render_occlusion(self.h, features.h, C.byref(params), int(first_pass), int(n_passes), C.c_uint32(seed), dst.h))
 
     def render_reserve(self, fb, task_rows, rank, world, MaxBounceCount, n_passes, sub_samples=4):
         """rtw_render_reserve: bins, tile tables and workspace of a later render_passes call with these arguments (renders nothing)"""

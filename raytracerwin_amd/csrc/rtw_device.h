@@ -193,6 +193,28 @@ struct QueryTuning {
 void query_launch_shape(const QueryTuning& q, long long n, int* threads, unsigned* blocks);
 int launch_shape_to_byte(const int* shape, long long n, uint8_t* out, hipStream_t stream);       // out[i] = shape[i] >= 0
 int launch_query(const RtwSceneDev* sc, const float* rays, long long n, float* hits11, int* shape, int* tri, uint8_t* occluded, const QueryTuning& q, bool stats, hipStream_t stream);
+// ---- ambient occlusion from the feature buffers (rtw_occlusion_kernels.h): one launch on `stream`, no workspace ----
+constexpr uint32_t OCCLUSION_COSINE = 1u;       // == RTW_OCCLUSION_COSINE of rtwin.h
+struct OcclusionCall {
+    const void *geom, *albedo, *ids;            // the features (never written)
+    void *accum, *argb;                         // the destination: accumulated into
+    const float* gamma_thr;
+    RtwCamera cam;
+    int width, height;
+    float radius, bias;
+    int samples;                                // 1..64
+    uint32_t flags;
+    int first_pass, n_passes;
+    uint32_t seed;
+    int order;                                  // 0 = a lane per pixel, 1 = a lane per sample, -1 = the measured rule (occlusion_is_by_sample)
+    int cu_count = 256;
+    bool single_mesh = false;                   // as QueryTuning's
+    int staged_shape = -1, staged_top = 0;
+    bool staged_all = false;
+};
+bool occlusion_is_by_sample(int order);
+void occlusion_launch_shape(const OcclusionCall& o, int* threads, unsigned* blocks, int* staged_top, bool* staged_all);
+int launch_occlusion(const RtwSceneDev* sc, const OcclusionCall& o, hipStream_t stream);
 int launch_ray_trace(const RtwSceneDev* sc, const float* rays, const uint32_t* keys2, long long n, int max_bounce, int preview,
                      uint32_t seed, unsigned long long npix, float* rgb, void* ws, bool stats, hipStream_t stream);
 int launch_texture_sample(const RtwSceneDev* sc, int shape, int mat, const float* uv, long long n, float* rgba, hipStream_t stream);

@@ -1122,6 +1122,7 @@ __global__ __launch_bounds__(256, 3) void shade_kernel(const RtwSceneDev* __rest
 #include "rtw_upsample_kernels.h"
 #include "rtw_budget_kernels.h"
 #include "rtw_query_kernels.h"
+#include "rtw_occlusion_kernels.h"
 #include "rtw_build_kernels.h"
 
 __global__ __launch_bounds__(256) void resolve_kernel(const RtwSceneDev* __restrict__ sc, float4* __restrict__ accum,
@@ -2008,6 +2009,50 @@ int launch_query(const RtwSceneDev* sc, const float* rays, long long n, float* h
         with_flags(stats, !q.single_mesh, occluded != nullptr, [&](auto ST, auto AN, auto ANY) {
             launch(qtrace_kernel<decltype(ST)::value, decltype(AN)::value, S::NT, S::CAP, S::STG, decltype(ANY)::value>, dim3(blocks), dim3(S::NT), S::lds(q.staged_top), stream,
                    sc, rays, (uint32_t)n, hits11, shape, tri, occluded, q.staged_shape, carry);
+        });
+    });
+    return (int)hipGetLastError();
+}
+
+// ---- ambient occlusion from the feature buffers (rtw_occlusion_kernels.h) -------------------------------------------------------------------
+// "occlusion_order" -1, as measured with tools/occlusion_bench.py at 1080p, 4 and 16 samples, radius 0.25 and 1000 (profiles/occlusion_experiments.md): the two
+// orders differ by less than their spread in seven of eight configurations, so: a lane per pixel
+bool occlusion_is_by_sample(int order) { return order < 0 ? false : order != 0; }
+
+// The block shape of a call: the trace kernels' three (with_trace_shape).  A staged block's LDS is its candidate lists, four tiles' words and as many
+// of the tree's upper records as the rest of 128 KiB holds (any prefix of them can be staged: the walk reads a record in LDS or in memory by its index)
+void occlusion_launch_shape(const OcclusionCall& o, int* threads, unsigned* blocks, int* staged_top, bool* staged_all)
+{
+    const long long tiles = (long long)((o.width + OC_TILE - 1) / OC_TILE) * (long long)((o.height + OC_TILE - 1) / OC_TILE);
+    const long long room = (131072 - (long long)RTW_GT_CAP_STAGED * 1024 * 4 - 4 * (long long)oc_group_words(o.samples) * 4) / 32;
+    int top = o.staged_shape >= 0 ? o.staged_top : 0;
+    if (top > room) top = (int)room;
+    const bool staged = top >= 64;
+    *staged_top = staged ? top : 0; *staged_all = staged && o.staged_all && top == o.staged_top;
+    const int nt = staged ? 1024 : 256;
+    long long most = (long long)o.cu_count * (staged ? 1 : 8);
+    const long long need = (tiles + nt / 256 - 1) / (nt / 256);
+    if (most > need) most = need;
+    if (most < 1) most = 1;
+    *threads = nt; *blocks = (unsigned)most;
+}
+
+int launch_occlusion(const RtwSceneDev* sc, const OcclusionCall& o, hipStream_t stream)
+{
+    if (o.width < 1 || o.height < 1 || o.samples < 1 || o.samples > 64 || o.n_passes < 1) return (int)hipErrorInvalidValue;
+    OcclusionBufs b;
+    b.geom = (const float4*)o.geom; b.albedo = (const float4*)o.albedo; b.ids = (const unsigned long long*)o.ids;
+    b.accum = (float4*)o.accum; b.argb = (uint32_t*)o.argb; b.gamma_thr = o.gamma_thr; b.cam = o.cam;
+    b.width = o.width; b.height = o.height; b.tiles_x = (o.width + OC_TILE - 1) / OC_TILE; b.n_tiles = b.tiles_x * ((o.height + OC_TILE - 1) / OC_TILE);
+    b.radius = o.radius; b.bias = o.bias; b.samples = o.samples; b.cosine = (o.flags & OCCLUSION_COSINE) ? 1 : 0;
+    b.first_pass = o.first_pass; b.n_passes = o.n_passes; b.seed = o.seed;
+    int nt, top; unsigned blocks; bool all;
+    occlusion_launch_shape(o, &nt, &blocks, &top, &all);
+    with_trace_shape(nt == 1024, all, [&](auto SH) {
+        using S = decltype(SH);
+        const size_t lds = S::lds(top) + (size_t)(S::NT / 256) * oc_group_words(o.samples) * 4;
+        with_flags(!o.single_mesh, occlusion_is_by_sample(o.order), [&](auto AN, auto BY) {
+            launch(occlusion_kernel<decltype(AN)::value, S::NT, S::CAP, S::STG, decltype(BY)::value>, dim3(blocks), dim3(S::NT), lds, stream, sc, b, o.staged_shape, top);
         });
     });
     return (int)hipGetLastError();

@@ -125,6 +125,50 @@ RTW_HD bool reproject_corner(float fx, float fy, int width, int height, int& x0,
     return true;
 }
 
+// ---- ambient occlusion from the feature buffers (rtw_render_occlusion of rtwin.h, steps 1 to 4) ----------------------------------------
+// Every product and every sum rounded on its own, in the order written; the tests' NumPy model repeats them.
+#define RTW_OC_EMPTY 0      // feature count 0: the pixel is not written
+#define RTW_OC_OPEN 1       // a miss, or a normal too short to aim by: no ray, a = 1 in every pass
+#define RTW_OC_CAST 2
+// The state of pixel (x, y) from its feature words -- (gx, gy, gz) the summed normal, gw the summed depth, cf their count, shape the id -- and, for a
+// casting pixel, the unit normal n and the origin O = P + n * bias of its rays
+RTW_HD int occlusion_origin(const RtwCamera& c, int x, int y, int width, int height, float gx, float gy, float gz, float gw, int cf, int shape, float bias, f3& O, f3& n)
+{
+    O = mk(0.0f, 0.0f, 0.0f); n = mk(0.0f, 0.0f, 0.0f);
+    if (cf == 0) return RTW_OC_EMPTY;
+    const float nf = (float)cf;
+    const float z = gw / nf;
+    const f3 m = mk(gx / nf, gy / nf, gz / nf);
+    if (shape < 0 || near_zero(m.x * m.x + m.y * m.y + m.z * m.z)) return RTW_OC_OPEN;
+    n = normalized(m);
+    const f3 P = reproject_point(c, x, y, width, height, z);
+    O = mk(P.x + n.x * bias, P.y + n.y * bias, P.z + n.z * bias);
+    return RTW_OC_CAST;
+}
+// the unit-table entry of sample s of pass k of a pixel: the first draw of the sample's own stream, modulo the table size (2^24 == 1 mod 2^24 - 1: the
+// two digits of a 31-bit draw add up to less than 2^24 + 2^7, so one subtraction ends it -- the value `%` gives)
+RTW_HD uint32_t occlusion_table_index(uint32_t seed, uint32_t pixel, uint32_t pass, uint32_t s)
+{
+    const uint32_t x = stream_draw31(stream_key(seed, pixel, (pass * 64u + s) | RTW_OCCLUSION_STREAM), 0u);
+    uint32_t i = (x & 0xFFFFFFu) + (x >> 24);
+    if (i >= RTW_TABLE_SIZE) i -= RTW_TABLE_SIZE;
+    return i;
+}
+// the table entry v turned into the hemisphere of n (RMath::PseudoRandomUnitVector's two lines, Src/Math.cpp:42-54; reflect is Src/RVector.h:218)
+RTW_HD f3 occlusion_direction(f3 v, f3 n)
+{
+    const float dt = dot(v, n);
+    if (dt > 0.0f) return v;
+    return mk(v.x - (n.x * 2.0f) * dt, v.y - (n.y * 2.0f) * dt, v.z - (n.z * 2.0f) * dt);
+}
+// a sample's weight: max(0, dot(n, d)) under RTW_OCCLUSION_COSINE (a NaN gives 0), else 1
+RTW_HD float occlusion_weight(f3 n, f3 d, bool cosine)
+{
+    if (!cosine) return 1.0f;
+    const float dt = dot(n, d);
+    return dt > 0.0f ? dt : 0.0f;
+}
+
 // ---- guided upsampling (rtw_upsample of rtwin.h, step 1) ------------------------------------------------------------------------------
 // Pixel x of a `size`-wide frame looks through the screen point (x - size / 2) / size (pixel_dx without its sign and scale); in a `low`-wide frame
 // of the same camera that point lies tx of the way from pixel x0 to pixel x0 + 1.  Integers up to the last division: n = (x - size / 2) * low,

@@ -181,6 +181,8 @@ struct RtwRenderParams {
 };
 // the lens point's random stream: stream_key(seed, pixel, (pass * 4 + sub) | RTW_LENS_STREAM), beside the path's own (whose counter the lens never moves)
 #define RTW_LENS_STREAM 0x80000000u
+// an occlusion sample's random stream (rtw_render_occlusion of rtwin.h): stream_key(seed, pixel, (pass * 64 + sample) | RTW_OCCLUSION_STREAM), pass < 2^24
+#define RTW_OCCLUSION_STREAM 0x40000000u
 
 // screen-space bins of one shape for one (width, height, tile shape): CSR over the bins, entries = node index of a leaf, ascending
 struct RtwBinsDev {

@@ -161,6 +161,7 @@ struct rtw_context {
     int variance_prefilter = -1;        // option: rtw_denoise_variance's g(p): 0 = fetched by the level kernels, 1 = a prefilter pass per level, -1 = the measured rule (rtw::denoise_variance_prefilter_is_pass); same bits either way
     int reproject_staging = -1;         // option: rtw_reproject's taps: 0 = from global memory, 1 = the block's tap box staged in LDS, -1 = the measured rule (rtw::reproject_is_staged); same bits either way
     int upsample_staging = -1;          // option: rtw_upsample's taps: 0 = from global memory, 1 = the tile's box of low-resolution records staged in LDS, -1 = the measured rule (rtw::upsample_is_staged); same bits either way
+    int occlusion_order = -1;           // option: rtw_render_occlusion's ray order: 0 = a lane per pixel, 1 = a lane per sample, -1 = the measured rule (rtw::occlusion_is_by_sample); same bits either way
 };
 
 struct rtw_scene {
@@ -388,6 +389,7 @@ int rtw_context_set_option(rtw_context* ctx, const char* name, int value)
     if (std::strcmp(name, "variance_prefilter") == 0) { ctx->variance_prefilter = value < 0 ? -1 : (value ? 1 : 0); return RTW_OK; }
     if (std::strcmp(name, "reproject_staging") == 0) { ctx->reproject_staging = value < 0 ? -1 : (value ? 1 : 0); return RTW_OK; }
     if (std::strcmp(name, "upsample_staging") == 0) { ctx->upsample_staging = value < 0 ? -1 : (value ? 1 : 0); return RTW_OK; }
+    if (std::strcmp(name, "occlusion_order") == 0) { ctx->occlusion_order = value < 0 ? -1 : (value ? 1 : 0); return RTW_OK; }
     if (std::strcmp(name, "material_variants") == 0) { ctx->material_variants = value ? 1 : 0; return RTW_OK; }
     if (std::strcmp(name, "lens_route") == 0) { ctx->lens_route = value < 0 ? -1 : (value ? 1 : 0); return RTW_OK; }
     if (std::strcmp(name, "query_blocks") == 0) { ctx->query_blocks = value < 0 ? 0 : value; return RTW_OK; }
@@ -2446,6 +2448,39 @@ int rtw_sample_budget(rtw_framebuffer* src, rtw_moments* m, const rtw_sample_bud
     s.min_history = p->min_history; s.min_passes = p->min_passes; s.max_passes = p->max_passes; s.radius = p->radius;
     const hipError_t e = (hipError_t)rtw::launch_sample_budget(s, cx->stream);
     if (e != hipSuccess) return hip_fail(e, "sample budget launch");
+    return RTW_OK;
+}
+
+// ---- ambient occlusion from the feature buffers (rtw_occlusion_kernels.h; the formula is rtwin.h's) -----------------------------------------
+int rtw_occlusion_default_params(rtw_occlusion_params* p)
+{
+    if (!p) return fail(RTW_ERR_INVALID, "null");
+    p->radius = 1.0f; p->bias = 1e-3f; p->samples = 8; p->flags = RTW_OCCLUSION_COSINE;
+    return RTW_OK;
+}
+
+int rtw_render_occlusion(rtw_scene* scene, rtw_features* f, const rtw_occlusion_params* p, int first_pass, int n_passes, uint32_t seed, rtw_framebuffer* dst)
+{
+    if (!scene || !f || !p || !dst) return fail(RTW_ERR_INVALID, "null argument");
+    rtw_context* cx = scene->ctx;
+    if (f->ctx != cx || dst->ctx != cx) return fail(RTW_ERR_INVALID, "the scene and the buffers belong to different contexts");
+    if (f->width != dst->width || f->height != dst->height) return fail(RTW_ERR_INVALID, "the features and the destination differ in size");
+    if (p->samples < 1 || p->samples > 64) return fail(RTW_ERR_INVALID, "samples must be 1..64");
+    if (!(p->radius > 0.0f)) return fail(RTW_ERR_INVALID, "radius must be positive");
+    if (!(p->bias >= 0.0f)) return fail(RTW_ERR_INVALID, "bias must not be negative");
+    if (p->flags & ~RTW_OCCLUSION_COSINE) return fail(RTW_ERR_INVALID, "unknown flag bits");
+    if (n_passes < 1 || first_pass < 0 || (int64_t)first_pass + n_passes > ((int64_t)1 << 24)) return fail(RTW_ERR_INVALID, "need n_passes >= 1, first_pass >= 0 and first_pass + n_passes <= 2^24");
+    const int rc = need_committed(scene); if (rc != RTW_OK) return rc;
+    HIP_TRY(hipSetDevice(cx->device));
+    rtw::OcclusionCall o;
+    o.geom = f->geom; o.albedo = f->albedo; o.ids = f->ids; o.accum = dst->accum; o.argb = dst->argb; o.gamma_thr = cx->d_gamma;
+    o.cam = scene->camera; o.width = dst->width; o.height = dst->height;
+    o.radius = p->radius; o.bias = p->bias; o.samples = p->samples; o.flags = p->flags;
+    o.first_pass = first_pass; o.n_passes = n_passes; o.seed = seed; o.order = cx->occlusion_order;
+    o.cu_count = cx->cu_count; o.single_mesh = scene->facts.single_mesh;
+    o.staged_shape = scene->facts.staged_shape; o.staged_top = scene->facts.staged_top; o.staged_all = scene->facts.staged_all;
+    const hipError_t e = (hipError_t)rtw::launch_occlusion(scene->d_scene, o, cx->stream);
+    if (e != hipSuccess) return hip_fail(e, "occlusion launch");
     return RTW_OK;
 }
 
