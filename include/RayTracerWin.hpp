@@ -318,6 +318,31 @@ inline void SampleBudget(ColorBuffer& Source, Moments& Mom, void* BudgetDev, con
 // rtw_occlusion_params for RayTracerScene::RenderOcclusion: radius 1, bias 1e-3, 8 samples per pass, cosine-weighted
 typedef rtw_occlusion_params OcclusionParams;
 inline OcclusionParams OcclusionDefaults() { OcclusionParams p; RtwCheck(rtw_occlusion_default_params(&p)); return p; }
+// The display transform's metering state on the device (rtw_exposure of rtwin.h): the exposure Tonemap maps the next frame with, adapted by every
+// metering call from the frame's log-luminance histogram
+class Exposure {
+public:
+    explicit Exposure(RtwDevice& dev) : E(nullptr) { RtwCheck(rtw_exposure_create(dev.Get(), &E)); }
+    ~Exposure() { rtw_exposure_destroy(E); }
+    rtw_exposure* Get() const { return E; }
+    void Reset() { RtwCheck(rtw_exposure_reset(E)); }
+    void Set(float Value) { RtwCheck(rtw_exposure_set(E, Value)); }
+    // the exposure, the frames metered and (Histogram may be NULL) the 256 bins of the last metered frame; waits for the device's stream
+    float Read(int32_t* Frames = nullptr, uint32_t* Histogram = nullptr) { float v = 0.0f; RtwCheck(rtw_exposure_read(E, &v, Frames, Histogram)); return v; }
+private:
+    Exposure(const Exposure&); Exposure& operator=(const Exposure&);
+    rtw_exposure* E;
+};
+// rtw_tonemap: Source mapped for display into Destination (which may be Source) -- exposed with the value Exp held before the call, a tone curve, the
+// gamma pack -- while the same launch meters Source and adapts Exp for the next frame.  Exp NULL: exposure 1, nothing metered.  Asynchronous, one launch.
+// MeterExposure is the metering alone, e.g. ahead of the first frame.  The formula and the parameters are rtwin.h's.
+typedef rtw_tonemap_params TonemapParams;
+inline TonemapParams TonemapDefaults() { TonemapParams p; RtwCheck(rtw_tonemap_default_params(&p)); return p; }
+inline void Tonemap(ColorBuffer& Source, Exposure* Exp, ColorBuffer& Destination, const TonemapParams& Params = TonemapDefaults())
+{
+    RtwCheck(rtw_tonemap(Source.Get(), Exp ? Exp->Get() : nullptr, &Params, Destination.Get()));
+}
+inline void MeterExposure(ColorBuffer& Source, Exposure& Exp, const TonemapParams& Params = TonemapDefaults()) { RtwCheck(rtw_exposure_meter(Source.Get(), Exp.Get(), &Params)); }
 
 // ---- Src/RayTracerScene.h --------------------------------------------------------------------------------------------------------
 class RayTracerScene {

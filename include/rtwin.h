@@ -104,6 +104,8 @@ int rtw_context_synchronize(rtw_context* ctx);
  *                   per level, -1 = the measured rule; same bits;
  *   "reproject_staging" (-1) where rtw_reproject's taps come from: 0 = global memory, 1 = the block's tap box staged in LDS, -1 = the measured rule; same bits;
  *   "upsample_staging" (-1) where rtw_upsample's taps come from: 0 = global memory, 1 = the tile's box of low-resolution records staged in LDS, -1 = the measured rule; same bits;
+ *   "tonemap_histogram" (-1) how a wave of rtw_tonemap / rtw_exposure_meter builds its histogram in LDS: 0 = an atomic per lane, 1 = one addition per distinct
+ *                   bin of the wave's pixels, -1 = the measured rule; same bits;  "tonemap_blocks" (0) > 0: those calls launch at most this many blocks;
  *   "query_kernel"  (-1) which kernel the device queries (rtw_trace_closest_device / rtw_trace_occluded_device / rtw_trace_occluded) run: 1 = the ray-per-lane
  *                   query kernel (rtw_query_kernels.h); 0 = the kernel of rtw_trace_closest on the caller's buffers (any-hit: a closest query whose
  *                   shape >= 0 becomes the byte) -- the A/B baseline and cross-check; -1 = the measured rule (profiles/query_experiments.md): any-hit on
@@ -596,6 +598,57 @@ typedef struct rtw_occlusion_params { float radius, bias; int samples; uint32_t 
 /* radius 1.0, bias 1e-3, samples 8, flags RTW_OCCLUSION_COSINE */
 int rtw_occlusion_default_params(rtw_occlusion_params* p);
 int rtw_render_occlusion(rtw_scene* scene, rtw_features* f, const rtw_occlusion_params* p, int first_pass, int n_passes, uint32_t seed, rtw_framebuffer* dst);
+
+/* ---- HDR display transform: histogram auto-exposure, a tone curve and the ARGB pack (no reference counterpart: its resolve divides, clamps and packs) ----
+ * The chain hands over linear radiance -- emitters, mirror paths onto emitters -- that a clamp to [0, 1] turns white, and a moving camera wants an
+ * exposure that follows the frame.  rtw_tonemap meters src with a log-luminance histogram, adapts the exposure of the rtw_exposure object, maps src with
+ * the exposure the object held BEFORE the call through a tone curve, and packs ARGB.  It takes buffers and no scene.  Every float product, sum and
+ * quotient is float32 and rounded on its own, in the order written; `double` where stated; integers elsewhere.  lum is rtw_denoise_variance's.
+ *  1 pixel colour    cnt = src.accum's int count.  A pixel with cnt == 0 is neither counted nor written.  c = sum.xyz / (float)cnt.
+ *  2 luminance       L = lum(c) = (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z.
+ *  3 bin             the pixel is COUNTED iff L > 0 and L is finite.  u = the bits of L;  bin = clamp((int)(u >> 20) - 856, 0, 255): 8 bins per octave,
+ *                    piecewise linear in log2, from 2^-20 to 2^12.  No logarithm is evaluated: h[k] = the number of counted pixels of bin k, exact.
+ *  4 new exposure    once, after the whole frame is binned.  N = sum h[k];  N == 0: the object stays as it is (exposure, frames and rtw_exposure_read's
+ *                    histogram).  lo = (uint32)((double)low_fraction * N),  hi = (uint32)((double)high_fraction * N);  hi <= lo: lo = 0, hi = N.
+ *                    P_k = h[0] + ... + h[k-1];  c_k = |[P_k, P_k + h[k]) n [lo, hi)|;  S = sum k * c_k (64-bit);  in double:
+ *                    m = (double)S / (double)(hi - lo),  t = (uint32)((m + 0.5 + 856.0) * 1048576.0) (truncated);  Lavg = the float whose bits are t.
+ *                    target = fminf(fmaxf(key / Lavg, min_exposure), max_exposure).
+ *                    unmetered object: E = target;  otherwise E = E + (target - E) * adapt.  frames += 1; the object is metered from now on.
+ *  5 mapping         E0 = the exposure the object held before this call (1.0f for e == NULL or after create / reset).  x = c * E0 per channel.
+ *                    RTW_TONEMAP_LINEAR    y = x
+ *                    RTW_TONEMAP_REINHARD  Lx = lum(x);  s = (1.0f + Lx / (white * white)) / (1.0f + Lx) when Lx > 0, else 1.0f;  y = x * s
+ *                    RTW_TONEMAP_ACES      per channel v = fmaxf(x, 0.0f);  y = (v * (2.51f * v + 0.03f)) / (v * (2.43f * v + 0.59f) + 0.14f)
+ *                    dst.accum = (y, count 1);  dst.argb = the gamma pack of y (rtw_gamma_thresholds, as rtw_denoise writes it): dst is then an
+ *                    ordinary one-pass framebuffer for every other call.  dst may be src.
+ * The one-frame latency of the exposure is deliberate: the new exposure needs the whole frame's histogram, and mapping with the previous one is what lets
+ * a frame be ONE launch that reads each accumulator entry once.  rtw_exposure_meter before the first frame removes it where it matters.
+ * With RTW_TONEMAP_HOLD the object's exposure is used and nothing is metered; with e == NULL the exposure is 1 and nothing is metered.
+ * Asynchronous on the context's stream: ONE launch, no work space, no allocation, copy or synchronisation.  The context option "tonemap_histogram" (-1)
+ * picks how a wave builds its histogram in LDS -- 0 = an atomic per lane, 1 = one addition per distinct bin of the wave's pixels, -1 = the faster by
+ * measurement -- and never changes a bit; "tonemap_blocks" (0) > 0 caps the launch's blocks.  One exposure object serves one call at a time.
+ * RTW_ERR_INVALID, nothing launched: a null src, params or dst (rtw_exposure_meter: a null e); differing sizes; handles of different contexts; an unknown
+ * curve; a NaN parameter; white <= 0; fractions outside 0 <= low_fraction < high_fraction <= 1; min_exposure > max_exposure; adapt outside [0, 1];
+ * unknown flag bits; RTW_TONEMAP_HOLD given to rtw_exposure_meter. */
+typedef struct rtw_exposure rtw_exposure;       /* device state: the running 256-bin histogram and its ticket, the exposure, the frames metered, the last frame's histogram */
+int rtw_exposure_create(rtw_context* ctx, rtw_exposure** out);      /* as after rtw_exposure_reset */
+int rtw_exposure_destroy(rtw_exposure* e);
+/* unmetered, exposure 1.0f, 0 frames, histogram 0; asynchronous on the context's stream */
+int rtw_exposure_reset(rtw_exposure* e);
+/* a manual exposure (not NaN): the object counts as metered, so a later metering call adapts from it; frames and histogram stay; asynchronous */
+int rtw_exposure_set(rtw_exposure* e, float exposure);
+/* waits for the context's stream.  hist256 = the histogram of the LAST metered frame.  Any output may be NULL. */
+int rtw_exposure_read(rtw_exposure* e, float* exposure, int32_t* frames, uint32_t hist256[256]);
+#define RTW_TONEMAP_LINEAR 0
+#define RTW_TONEMAP_REINHARD 1
+#define RTW_TONEMAP_ACES 2
+#define RTW_TONEMAP_HOLD 1u     /* use the object's exposure, do not meter */
+typedef struct rtw_tonemap_params { int curve; float key, white, low_fraction, high_fraction, min_exposure, max_exposure, adapt; uint32_t flags; } rtw_tonemap_params;
+/* RTW_TONEMAP_ACES, key 0.18 (the luminance the metered average is brought to), white 4 (Reinhard: the exposed luminance that maps to 1), the pixels
+ * between the 50th and the 95th percentile metered, exposure within [1/64, 64], adapt 0.25 (a quarter of the way to the target per frame), no flag */
+int rtw_tonemap_default_params(rtw_tonemap_params* p);
+/* steps 1 to 4 alone: meters src into e and writes no image */
+int rtw_exposure_meter(rtw_framebuffer* src, rtw_exposure* e, const rtw_tonemap_params* p);
+int rtw_tonemap(rtw_framebuffer* src, rtw_exposure* e, const rtw_tonemap_params* p, rtw_framebuffer* dst);
 
 /* Device memory the context holds: workspaces + its share of the 201 MB unit-vector table (one copy per device, shared by the contexts on it).
  * The workspace is sized by the largest group of passes rendered (or reserved) so far: per path slot 116 B + 48 B x max_bounce, slots = pixels of the

@@ -652,6 +652,70 @@ class OcclusionParams(C.Structure):
             setattr(self, k, v)
 
 
+class TonemapParams(C.Structure):
+    """rtw_tonemap_params; TonemapParams() holds rtw_tonemap_default_params' values (ACES, 0.18, 4.0, 0.5, 0.95, 1/64, 64, 0.25, no flag), keywords override them"""
+    _fields_ = [("curve", C.c_int), ("key", C.c_float), ("white", C.c_float), ("low_fraction", C.c_float), ("high_fraction", C.c_float),
+                ("min_exposure", C.c_float), ("max_exposure", C.c_float), ("adapt", C.c_float), ("flags", C.c_uint32)]
+    LINEAR, REINHARD, ACES = 0, 1, 2
+    HOLD = 1
+
+    def __init__(self, **kw):
+        super().__init__()
+        _check(library().rtw_tonemap_default_params(C.byref(self)))
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+class Exposure:
+    """The display transform's metering state on the device (rtw_exposure of include/rtwin.h): the exposure tonemap() maps the next frame with, adapted by
+    every metering call from the frame's log-luminance histogram."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        ctx._children.add(self)
+        _check(library().rtw_exposure_create(ctx.h, C.byref(self.h)))
+
+    def reset(self):
+        """unmetered, exposure 1, no frames; asynchronous"""
+        _check(library().rtw_exposure_reset(self.h))
+
+    def set(self, exposure):
+        """a manual exposure, from which a later metering call adapts; asynchronous"""
+        _check(library().rtw_exposure_set(self.h, C.c_float(exposure)))
+
+    def read(self):
+        """(exposure float32, frames metered, (256,) uint32 histogram of the last metered frame); waits for the context's stream"""
+        e, n, hist = C.c_float(), C.c_int32(), np.empty(256, np.uint32)
+        _check(library().rtw_exposure_read(self.h, C.byref(e), C.byref(n), _p(hist)))
+        return np.float32(e.value), n.value, hist
+
+    def close(self):
+        if getattr(self, "h", None):
+            library().rtw_exposure_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def tonemap(src, dst, exposure=None, params=None):
+    """rtw_tonemap: the Framebuffer src mapped for display into the Framebuffer dst (which may be src) -- exposed with the value the Exposure held before
+    the call, a tone curve, the gamma pack -- while the same launch meters src and adapts the Exposure for the next frame (the formula is
+    include/rtwin.h's).  exposure=None: exposure 1, nothing metered.  dst is afterwards an ordinary one-pass framebuffer.  Asynchronous, one launch."""
+    params = params if params is not None else TonemapParams()
+    _check(library().rtw_tonemap(src.h, exposure.h if exposure is not None else None, C.byref(params), dst.h))
+
+
+def meter_exposure(src, exposure, params=None):
+    """rtw_exposure_meter: tonemap()'s metering alone -- no image is written -- e.g. ahead of the first frame, which is otherwise mapped with exposure 1"""
+    params = params if params is not None else TonemapParams()
+    _check(library().rtw_exposure_meter(src.h, exposure.h, C.byref(params)))
+
+
 class DenoiseVarianceParams(C.Structure):
     """rtw_denoise_variance_params; DenoiseVarianceParams() holds rtw_denoise_variance_default_params' values (5, 4.0, 0.3, 0.1, both flags, 4)"""
     _fields_ = [("levels", C.c_int), ("sigma_lum", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("flags", C.c_uint32), ("min_history", C.c_int)]

@@ -215,6 +215,33 @@ struct OcclusionCall {
 bool occlusion_is_by_sample(int order);
 void occlusion_launch_shape(const OcclusionCall& o, int* threads, unsigned* blocks, int* staged_top, bool* staged_all);
 int launch_occlusion(const RtwSceneDev* sc, const OcclusionCall& o, hipStream_t stream);
+// ---- the HDR display transform (rtw_tonemap_kernels.h): histogram metering, exposure, tone curve and pack in one launch on `stream`, no workspace ----
+constexpr int TONEMAP_LINEAR = 0, TONEMAP_REINHARD = 1, TONEMAP_ACES = 2;      // == RTW_TONEMAP_* of rtwin.h
+constexpr int TONEMAP_BIN0 = 856;               // bin = (float bits >> 20) - 856: 8 bins per octave from 2^-20
+// the 32-bit words of an exposure object's device state
+constexpr int EXPOSURE_HIST = 0;                // 256: the running launch's histogram; zero between launches
+constexpr int EXPOSURE_LAST = 256;              // 256: the histogram of the last metered frame
+constexpr int EXPOSURE_TICKET = 512;            // blocks of the running launch that have filed their bins; zero between launches
+constexpr int EXPOSURE_VALUE = 513;             // the exposure's float bits
+constexpr int EXPOSURE_METERED = 514;           // 0 until a frame was metered or an exposure set
+constexpr int EXPOSURE_FRAMES = 515;            // frames metered
+constexpr int EXPOSURE_WORDS = 516;
+struct TonemapCall {
+    const void* src_accum;
+    void *dst_accum, *dst_argb;                 // null for meter-only (write false); may be the source's
+    const float* gamma_thr;
+    uint32_t* state;                            // the exposure object's words; null: exposure 1, no metering
+    int width, height, curve;
+    float key, white, low_fraction, high_fraction, min_exposure, max_exposure, adapt;
+    bool meter, write;
+    int histogram;                              // 0 = an LDS atomic per lane, 1 = wave-aggregated, -1 = the measured rule (tonemap_histogram_is_aggregated)
+    int cu_count = 256;
+    int blocks = 0;                             // > 0: at most this many blocks (option "tonemap_blocks")
+};
+bool tonemap_histogram_is_aggregated(int option);
+unsigned tonemap_blocks(const TonemapCall& c);
+int launch_tonemap(const TonemapCall& c, hipStream_t stream);
+int launch_exposure_state(uint32_t* state, float exposure, bool metered, bool clear, hipStream_t stream);
 int launch_ray_trace(const RtwSceneDev* sc, const float* rays, const uint32_t* keys2, long long n, int max_bounce, int preview,
                      uint32_t seed, unsigned long long npix, float* rgb, void* ws, bool stats, hipStream_t stream);
 int launch_texture_sample(const RtwSceneDev* sc, int shape, int mat, const float* uv, long long n, float* rgba, hipStream_t stream);

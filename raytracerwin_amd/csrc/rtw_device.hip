@@ -1123,6 +1123,7 @@ __global__ __launch_bounds__(256, 3) void shade_kernel(const RtwSceneDev* __rest
 #include "rtw_budget_kernels.h"
 #include "rtw_query_kernels.h"
 #include "rtw_occlusion_kernels.h"
+#include "rtw_tonemap_kernels.h"
 #include "rtw_build_kernels.h"
 
 __global__ __launch_bounds__(256) void resolve_kernel(const RtwSceneDev* __restrict__ sc, float4* __restrict__ accum,
@@ -2055,6 +2056,48 @@ int launch_occlusion(const RtwSceneDev* sc, const OcclusionCall& o, hipStream_t 
             launch(occlusion_kernel<decltype(AN)::value, S::NT, S::CAP, S::STG, decltype(BY)::value>, dim3(blocks), dim3(S::NT), lds, stream, sc, b, o.staged_shape, top);
         });
     });
+    return (int)hipGetLastError();
+}
+
+// ---- the HDR display transform (rtw_tonemap_kernels.h) ----------------------------------------------------------------------------------------
+// "tonemap_histogram" -1, as measured with tools/tonemap_bench.py at 1080p and 2160p (profiles/tonemap_experiments.md): on a rendered frame an LDS atomic per
+// lane is 17 to 22 % faster than the wave-aggregated loop, on a flat frame (every pixel in one bin) the two are within 3 % of each other, so: a lane per count
+bool tonemap_histogram_is_aggregated(int option) { return option < 0 ? false : option != 0; }
+
+// A persistent grid: a chunk of 1024 pixels per block until there are three blocks to a CU, from there on the blocks stride; the option "tonemap_blocks"
+// caps it.  Three, as measured: a metering block ends with a release fence, an L2 write-back that costs the more the more blocks there are (eight to a CU
+// took twice as long at both sizes), and without metering three blocks to a CU already stream at the rate of eight
+unsigned tonemap_blocks(const TonemapCall& c)
+{
+    long long most = (long long)c.cu_count * 3;
+    if (c.blocks > 0 && c.blocks < most) most = c.blocks;
+    return blocks_of((long long)c.width * (long long)c.height, TM_CHUNK, most);
+}
+
+int launch_tonemap(const TonemapCall& c, hipStream_t stream)
+{
+    if (c.width < 1 || c.height < 1 || (long long)c.width * c.height > (1ll << 30) || (c.meter && !c.state) || (!c.meter && !c.write)) return (int)hipErrorInvalidValue;
+    TonemapBufs b;
+    b.src = (const float4*)c.src_accum; b.dst_accum = (float4*)c.dst_accum; b.dst_argb = (uint32_t*)c.dst_argb; b.gamma_thr = c.gamma_thr; b.state = c.state;
+    b.n = (uint32_t)((long long)c.width * c.height);
+    b.key = c.key; b.white = c.white; b.low_fraction = c.low_fraction; b.high_fraction = c.high_fraction;
+    b.min_exposure = c.min_exposure; b.max_exposure = c.max_exposure; b.adapt = c.adapt;
+    b.aggregate = tonemap_histogram_is_aggregated(c.histogram) ? 1 : 0;
+    const dim3 grid(tonemap_blocks(c));
+    auto go = [&](auto CU) {
+        with_flags(c.meter, [&](auto ME) { launch(tonemap_kernel<decltype(CU)::value, decltype(ME)::value, true>, grid, dim3(256), 0, stream, b); });
+    };
+    if (!c.write) launch(tonemap_kernel<TONEMAP_LINEAR, true, false>, grid, dim3(256), 0, stream, b);
+    else if (c.curve == TONEMAP_LINEAR) go(std::integral_constant<int, TONEMAP_LINEAR>{});
+    else if (c.curve == TONEMAP_REINHARD) go(std::integral_constant<int, TONEMAP_REINHARD>{});
+    else if (c.curve == TONEMAP_ACES) go(std::integral_constant<int, TONEMAP_ACES>{});
+    else return (int)hipErrorInvalidValue;
+    return (int)hipGetLastError();
+}
+
+int launch_exposure_state(uint32_t* state, float exposure, bool metered, bool clear, hipStream_t stream)
+{
+    launch(exposure_state_kernel, dim3(1), dim3(256), 0, stream, state, exposure, metered ? 1u : 0u, clear ? 1 : 0);
     return (int)hipGetLastError();
 }
 

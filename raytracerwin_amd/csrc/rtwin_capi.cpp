@@ -162,6 +162,8 @@ struct rtw_context {
     int reproject_staging = -1;         // option: rtw_reproject's taps: 0 = from global memory, 1 = the block's tap box staged in LDS, -1 = the measured rule (rtw::reproject_is_staged); same bits either way
     int upsample_staging = -1;          // option: rtw_upsample's taps: 0 = from global memory, 1 = the tile's box of low-resolution records staged in LDS, -1 = the measured rule (rtw::upsample_is_staged); same bits either way
     int occlusion_order = -1;           // option: rtw_render_occlusion's ray order: 0 = a lane per pixel, 1 = a lane per sample, -1 = the measured rule (rtw::occlusion_is_by_sample); same bits either way
+    int tonemap_histogram = -1;         // option: rtw_tonemap's histogram in LDS: 0 = an atomic per lane, 1 = wave-aggregated, -1 = the measured rule (rtw::tonemap_histogram_is_aggregated); same bits either way
+    int tonemap_blocks = 0;             // option: > 0 = rtw_tonemap launches at most this many blocks (few pixels then make many trips of its chunk loop)
 };
 
 struct rtw_scene {
@@ -224,6 +226,11 @@ struct rtw_moments {        // luminance moments: float2 (mu1, mu2) per pixel
     int width = 0, height = 0;
     void* mu = nullptr;
     bool owned = false;
+};
+
+struct rtw_exposure {       // the display transform's metering state: rtw::EXPOSURE_WORDS words of device memory
+    rtw_context* ctx = nullptr;
+    uint32_t* state = nullptr;
 };
 
 struct rtw_features {       // first-hit feature buffers: geom / albedo float4 per pixel, ids int32 x 2 per pixel
@@ -390,6 +397,8 @@ int rtw_context_set_option(rtw_context* ctx, const char* name, int value)
     if (std::strcmp(name, "reproject_staging") == 0) { ctx->reproject_staging = value < 0 ? -1 : (value ? 1 : 0); return RTW_OK; }
     if (std::strcmp(name, "upsample_staging") == 0) { ctx->upsample_staging = value < 0 ? -1 : (value ? 1 : 0); return RTW_OK; }
     if (std::strcmp(name, "occlusion_order") == 0) { ctx->occlusion_order = value < 0 ? -1 : (value ? 1 : 0); return RTW_OK; }
+    if (std::strcmp(name, "tonemap_histogram") == 0) { ctx->tonemap_histogram = value < 0 ? -1 : (value ? 1 : 0); return RTW_OK; }
+    if (std::strcmp(name, "tonemap_blocks") == 0) { ctx->tonemap_blocks = value < 0 ? 0 : value; return RTW_OK; }
     if (std::strcmp(name, "material_variants") == 0) { ctx->material_variants = value ? 1 : 0; return RTW_OK; }
     if (std::strcmp(name, "lens_route") == 0) { ctx->lens_route = value < 0 ? -1 : (value ? 1 : 0); return RTW_OK; }
     if (std::strcmp(name, "query_blocks") == 0) { ctx->query_blocks = value < 0 ? 0 : value; return RTW_OK; }
@@ -2483,6 +2492,103 @@ int rtw_render_occlusion(rtw_scene* scene, rtw_features* f, const rtw_occlusion_
     if (e != hipSuccess) return hip_fail(e, "occlusion launch");
     return RTW_OK;
 }
+
+// ---- the HDR display transform (rtw_tonemap_kernels.h; the formula is rtwin.h's) ---------------------------------------------------------------
+int rtw_exposure_create(rtw_context* ctx, rtw_exposure** out)
+{
+    if (!ctx || !out) return fail(RTW_ERR_INVALID, "null argument");
+    HIP_TRY(hipSetDevice(ctx->device));
+    std::unique_ptr<rtw_exposure> e(new rtw_exposure());
+    e->ctx = ctx;
+    HIP_TRY(hipMalloc((void**)&e->state, rtw::EXPOSURE_WORDS * sizeof(uint32_t)));
+    const int rc = rtw_exposure_reset(e.get());
+    if (rc != RTW_OK) { (void)hipFree(e->state); return rc; }
+    *out = e.release();
+    return RTW_OK;
+}
+
+int rtw_exposure_destroy(rtw_exposure* e)
+{
+    if (!e) return RTW_OK;
+    (void)hipSetDevice(e->ctx->device);
+    (void)hipStreamSynchronize(e->ctx->stream);
+    (void)hipFree(e->state);
+    delete e;
+    return RTW_OK;
+}
+
+int rtw_exposure_reset(rtw_exposure* e)
+{
+    if (!e) return fail(RTW_ERR_INVALID, "exposure object is null");
+    HIP_TRY(hipSetDevice(e->ctx->device));
+    const hipError_t rc = (hipError_t)rtw::launch_exposure_state(e->state, 1.0f, false, true, e->ctx->stream);
+    if (rc != hipSuccess) return hip_fail(rc, "exposure reset launch");
+    return RTW_OK;
+}
+
+int rtw_exposure_set(rtw_exposure* e, float exposure)
+{
+    if (!e) return fail(RTW_ERR_INVALID, "exposure object is null");
+    if (std::isnan(exposure)) return fail(RTW_ERR_INVALID, "the exposure is NaN");
+    HIP_TRY(hipSetDevice(e->ctx->device));
+    const hipError_t rc = (hipError_t)rtw::launch_exposure_state(e->state, exposure, true, false, e->ctx->stream);
+    if (rc != hipSuccess) return hip_fail(rc, "exposure set launch");
+    return RTW_OK;
+}
+
+int rtw_exposure_read(rtw_exposure* e, float* exposure, int32_t* frames, uint32_t hist256[256])
+{
+    if (!e) return fail(RTW_ERR_INVALID, "exposure object is null");
+    HIP_TRY(hipSetDevice(e->ctx->device));
+    uint32_t w[rtw::EXPOSURE_WORDS];
+    HIP_TRY(hipMemcpyAsync(w, e->state, sizeof w, hipMemcpyDeviceToHost, e->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(e->ctx->stream));
+    if (exposure) std::memcpy(exposure, &w[rtw::EXPOSURE_VALUE], 4);
+    if (frames) *frames = (int32_t)w[rtw::EXPOSURE_FRAMES];
+    if (hist256) std::memcpy(hist256, &w[rtw::EXPOSURE_LAST], 256 * sizeof(uint32_t));
+    return RTW_OK;
+}
+
+int rtw_tonemap_default_params(rtw_tonemap_params* p)
+{
+    if (!p) return fail(RTW_ERR_INVALID, "null");
+    p->curve = RTW_TONEMAP_ACES; p->key = 0.18f; p->white = 4.0f; p->low_fraction = 0.5f; p->high_fraction = 0.95f;
+    p->min_exposure = 0.015625f; p->max_exposure = 64.0f; p->adapt = 0.25f; p->flags = 0u;
+    return RTW_OK;
+}
+
+// the checks rtw_tonemap and rtw_exposure_meter share, and the launch (dst null: meter only)
+static int tonemap_call(rtw_framebuffer* src, rtw_exposure* e, const rtw_tonemap_params* p, rtw_framebuffer* dst, bool write)
+{
+    if (!src || !p || (write ? !dst : !e)) return fail(RTW_ERR_INVALID, "null argument");
+    rtw_context* cx = src->ctx;
+    if ((dst && dst->ctx != cx) || (e && e->ctx != cx)) return fail(RTW_ERR_INVALID, "the buffers and the exposure object belong to different contexts");
+    if (dst && (dst->width != src->width || dst->height != src->height)) return fail(RTW_ERR_INVALID, "source and destination differ in size");
+    if (p->curve != RTW_TONEMAP_LINEAR && p->curve != RTW_TONEMAP_REINHARD && p->curve != RTW_TONEMAP_ACES) return fail(RTW_ERR_INVALID, "unknown curve");
+    if (std::isnan(p->key) || std::isnan(p->white) || std::isnan(p->low_fraction) || std::isnan(p->high_fraction) || std::isnan(p->min_exposure) ||
+        std::isnan(p->max_exposure) || std::isnan(p->adapt)) return fail(RTW_ERR_INVALID, "a parameter is NaN");
+    if (!(p->white > 0.0f)) return fail(RTW_ERR_INVALID, "white must be positive");
+    if (!(p->low_fraction >= 0.0f && p->low_fraction < p->high_fraction && p->high_fraction <= 1.0f)) return fail(RTW_ERR_INVALID, "need 0 <= low_fraction < high_fraction <= 1");
+    if (p->min_exposure > p->max_exposure) return fail(RTW_ERR_INVALID, "min_exposure exceeds max_exposure");
+    if (!(p->adapt >= 0.0f && p->adapt <= 1.0f)) return fail(RTW_ERR_INVALID, "adapt must lie in [0, 1]");
+    if (p->flags & ~RTW_TONEMAP_HOLD) return fail(RTW_ERR_INVALID, "unknown flag bits");
+    if (!write && (p->flags & RTW_TONEMAP_HOLD)) return fail(RTW_ERR_INVALID, "RTW_TONEMAP_HOLD leaves rtw_exposure_meter nothing to do");
+    HIP_TRY(hipSetDevice(cx->device));
+    rtw::TonemapCall c;
+    c.src_accum = src->accum; c.dst_accum = dst ? dst->accum : nullptr; c.dst_argb = dst ? dst->argb : nullptr; c.gamma_thr = cx->d_gamma;
+    c.state = e ? e->state : nullptr; c.width = src->width; c.height = src->height; c.curve = p->curve;
+    c.key = p->key; c.white = p->white; c.low_fraction = p->low_fraction; c.high_fraction = p->high_fraction;
+    c.min_exposure = p->min_exposure; c.max_exposure = p->max_exposure; c.adapt = p->adapt;
+    c.meter = e && !(p->flags & RTW_TONEMAP_HOLD); c.write = write;
+    c.histogram = cx->tonemap_histogram; c.cu_count = cx->cu_count; c.blocks = cx->tonemap_blocks;
+    const hipError_t rc = (hipError_t)rtw::launch_tonemap(c, cx->stream);
+    if (rc != hipSuccess) return hip_fail(rc, "tonemap launch");
+    return RTW_OK;
+}
+
+int rtw_exposure_meter(rtw_framebuffer* src, rtw_exposure* e, const rtw_tonemap_params* p) { return tonemap_call(src, e, p, nullptr, false); }
+
+int rtw_tonemap(rtw_framebuffer* src, rtw_exposure* e, const rtw_tonemap_params* p, rtw_framebuffer* dst) { return tonemap_call(src, e, p, dst, true); }
 
 // device memory this context holds right now: the group workspaces, the older pipelines' workspace and its share of the unit-vector table
 // (201 MB per device, shared by the contexts on it); scenes and framebuffers are the caller's objects and not counted
