@@ -318,6 +318,19 @@ inline void SampleBudget(ColorBuffer& Source, Moments& Mom, void* BudgetDev, con
 // rtw_occlusion_params for RayTracerScene::RenderOcclusion: radius 1, bias 1e-3, 8 samples per pass, cosine-weighted
 typedef rtw_occlusion_params OcclusionParams;
 inline OcclusionParams OcclusionDefaults() { OcclusionParams p; RtwCheck(rtw_occlusion_default_params(&p)); return p; }
+// rtw_light (Src/Light.h's point and directional lights) and rtw_lighting_params (bias 1e-3, 1 sample per light and pass, albedo on) for
+// RayTracerScene::RenderLighting
+typedef rtw_light Light;
+typedef rtw_lighting_params LightingParams;
+inline LightingParams LightingDefaults() { LightingParams p; RtwCheck(rtw_lighting_default_params(&p)); return p; }
+inline Light MakeLight(int Type, const RVec3& PositionOrDirection, const RVec3& Color, float Radius = 0.0f, uint32_t Flags = 0u)
+{
+    Light l;
+    l.type = Type; l.flags = Flags; l.radius = Radius;
+    l.v[0] = PositionOrDirection.x; l.v[1] = PositionOrDirection.y; l.v[2] = PositionOrDirection.z;
+    l.color[0] = Color.x; l.color[1] = Color.y; l.color[2] = Color.z;
+    return l;
+}
 // The display transform's metering state on the device (rtw_exposure of rtwin.h): the exposure Tonemap maps the next frame with, adapted by every
 // metering call from the frame's log-luminance histogram
 class Exposure {
@@ -436,6 +449,13 @@ public:
     {
         Commit();
         RtwCheck(rtw_render_occlusion(Scene, Features.Get(), &Params, FirstPass, NumPasses, Seed, Destination.Get()));
+    }
+    // Direct light of Lights (at most 8) on what Features show, under the current camera: per light the cosine times the unoccluded share of
+    // Params.samples shadow rays, the passes accumulated into Destination like render passes.  Asynchronous, one launch: rtw_render_lighting
+    void RenderLighting(FeatureBuffers& Features, const std::vector<Light>& Lights, const LightingParams& Params, int FirstPass, int NumPasses, uint32_t Seed, ColorBuffer& Destination)
+    {
+        Commit();
+        RtwCheck(rtw_render_lighting(Scene, Features.Get(), Lights.data(), (int)Lights.size(), &Params, FirstPass, NumPasses, Seed, Destination.Get()));
     }
     void Commit() { if (!Committed) { RtwCheck(rtw_scene_commit(Scene)); Committed = true; } }
     rtw_scene* Get() { Commit(); return Scene; }

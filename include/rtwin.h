@@ -599,6 +599,48 @@ typedef struct rtw_occlusion_params { float radius, bias; int samples; uint32_t 
 int rtw_occlusion_default_params(rtw_occlusion_params* p);
 int rtw_render_occlusion(rtw_scene* scene, rtw_features* f, const rtw_occlusion_params* p, int first_pass, int n_passes, uint32_t seed, rtw_framebuffer* dst);
 
+/* ---- direct lighting from the feature buffers: the reference's point and directional lights, shadowed (Src/Light.h, RayTracerScene::CalculateLightColor,
+ * which it ships switched off: USE_LIGHTS 0) ----
+ * Per pixel and pass: the sum over up to 8 lights of colour x max(0, n.d) x the unoccluded share of `samples` shadow rays.  The frame is W x H, shared by f
+ * and dst, in the scene's context; the camera is the scene's current camera.  Everything is float32, every product and every sum rounded on its own, in the
+ * order written.
+ *  1 pixel states    EMPTY / OPEN / CAST, the unit normal n, the surface point P and the origin O = P + n * bias: rtw_render_occlusion's steps 1 to 3.  An
+ *                    EMPTY pixel is not written.  An OPEN pixel (sky, no usable normal) takes e = (1, 1, 1) in every pass.
+ *  2 samples         for pass k = first_pass .. first_pass + n_passes - 1, light j = 0 .. n_lights - 1 and sample s = 0 .. samples - 1:  u = (0, 0, 0) when
+ *                    light.radius == 0, else key = stream_key(seed, pixel, (k * 64 + s) | 0xC0000000) with pixel = y * W + x;
+ *                    idx = stream_draw31(key, j) mod RTW_UNIT_TABLE_SIZE;  u = rtw_unit_table_entry(idx) (no phase, no debug mask).
+ *  3 point light     T = v + u * radius per component;  D = T - O;  dist = sqrt(dot(D, D));  d = D * (1 / dist);  dist == 0 or not finite: c = 0.
+ *                    att = 1 / (dist * dist) with RTW_LIGHT_INVERSE_SQUARE, else 1 (the reference has no falloff).
+ *  4 directional     v is the direction from the surface towards the light (the reference's PositionOrDirection):  D = v + u * radius;
+ *                    d = D * (1 / sqrt(dot(D, D)));  dist = 1000 (the reference's);  att = 1.
+ *  5 cosine, cull    c = dot(n, d).  Unless c > 0 (false for a NaN too) t = 0 and NO RAY EXISTS.
+ *  6 shadow ray      otherwise the ray is (O, d, dist);  o = 1 where rtw_trace_occluded would report it occluded;  t = o ? 0 : c * att.
+ *  7 per light       vis_j = (t_0 + t_1 + ...) / samples, summed left to right from +0.
+ *  8 per pass        e += color_j * vis_j per channel, in light order, from +0.  With RTW_LIGHTING_ALBEDO e *= (albedo.xyz / cf) per channel, cf the int
+ *                    count in f.albedo.w (the reference's InSurfaceColor * ldp); an OPEN pixel then takes the albedo mean itself: the sky colour.
+ *  9 accumulation    per pass, in order: dst.accum.xyz += e, count += 1.  After the call's last pass dst.argb is the gamma pack of accum.xyz / count.  Calls
+ *                    accumulate until rtw_framebuffer_clear; dst is an ordinary framebuffer for every other call (rtw_denoise*, rtw_reproject*, rtw_upsample,
+ *                    rtw_tonemap, the reads, the resolve and the PNG writer).
+ * The result depends on the scene, the camera, f, the lights, the parameters, the passes and the seed only.  The context option "lighting_deal" (-1) picks how
+ * the (pixel, light, sample) jobs are dealt to the lanes -- 0 = positional: a lane per pixel, a culled job idles through the walk; 1 = compacted: the jobs that
+ * survive step 5 are queued and walked 64 at a time; -1 = the faster by measurement -- and never changes a bit.  Limits: 8 lights, 8 samples, a static scene
+ * (the scene as committed), and under a lens P is still the pinhole's point, as for occlusion.
+ * `lights` is host memory, copied into the launch's arguments (at most 8 x 36 bytes).  f is not written.  Asynchronous on the context's stream: ONE launch
+ * whatever n_passes is (a pixel's accumulator entry is read once and written once), no work space, no allocation, copy or synchronisation.  The work counters
+ * (rtw_stats) do not count these rays.
+ * RTW_ERR_STATE: the scene is not committed.  RTW_ERR_INVALID, with dst untouched: everything rtw_render_occlusion refuses; n_lights outside 1..8; samples
+ * outside 1..8; an unknown type or flag bits; a v, color or radius that is not finite; radius < 0; a directional v whose squared length is not within 1e-3
+ * of 1; RTW_LIGHT_INVERSE_SQUARE on a directional light. */
+#define RTW_LIGHT_POINT 0
+#define RTW_LIGHT_DIRECTIONAL 1
+#define RTW_LIGHT_INVERSE_SQUARE 1u          /* per light, point lights only */
+typedef struct rtw_light { int type; uint32_t flags; float v[3]; float color[3]; float radius; } rtw_light;
+#define RTW_LIGHTING_ALBEDO 1u
+typedef struct rtw_lighting_params { float bias; int samples; uint32_t flags; } rtw_lighting_params;
+/* bias 1e-3, samples 1, flags RTW_LIGHTING_ALBEDO */
+int rtw_lighting_default_params(rtw_lighting_params* p);
+int rtw_render_lighting(rtw_scene* scene, rtw_features* f, const rtw_light* lights, int n_lights, const rtw_lighting_params* p, int first_pass, int n_passes, uint32_t seed, rtw_framebuffer* dst);
+
 /* ---- HDR display transform: histogram auto-exposure, a tone curve and the ARGB pack (no reference counterpart: its resolve divides, clamps and packs) ----
  * The chain hands over linear radiance -- emitters, mirror paths onto emitters -- that a clamp to [0, 1] turns white, and a moving camera wants an
  * exposure that follows the frame.  rtw_tonemap meters src with a log-luminance histogram, adapts the exposure of the rtw_exposure object, maps src with

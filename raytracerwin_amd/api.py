@@ -716,6 +716,32 @@ def meter_exposure(src, exposure, params=None):
     _check(library().rtw_exposure_meter(src.h, exposure.h, C.byref(params)))
 
 
+class Light(C.Structure):
+    """rtw_light: Light.point((x, y, z), color, radius, inverse_square) or Light.directional(unit direction towards the light, color, radius)"""
+    _fields_ = [("type", C.c_int), ("flags", C.c_uint32), ("v", C.c_float * 3), ("color", C.c_float * 3), ("radius", C.c_float)]
+    POINT, DIRECTIONAL, INVERSE_SQUARE = 0, 1, 1
+
+    @classmethod
+    def point(cls, position, color=(1.0, 1.0, 1.0), radius=0.0, inverse_square=False):
+        return cls(cls.POINT, cls.INVERSE_SQUARE if inverse_square else 0, tuple(position), tuple(color), radius)
+
+    @classmethod
+    def directional(cls, direction, color=(1.0, 1.0, 1.0), radius=0.0):
+        return cls(cls.DIRECTIONAL, 0, tuple(direction), tuple(color), radius)
+
+
+class LightingParams(C.Structure):
+    """rtw_lighting_params; LightingParams() holds rtw_lighting_default_params' values (1e-3, 1, ALBEDO), keywords override them"""
+    _fields_ = [("bias", C.c_float), ("samples", C.c_int), ("flags", C.c_uint32)]
+    ALBEDO = 1
+
+    def __init__(self, **kw):
+        super().__init__()
+        _check(library().rtw_lighting_default_params(C.byref(self)))
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
 class DenoiseVarianceParams(C.Structure):
     """rtw_denoise_variance_params; DenoiseVarianceParams() holds rtw_denoise_variance_default_params' values (5, 4.0, 0.3, 0.1, both flags, 4)"""
     _fields_ = [("levels", C.c_int), ("sigma_lum", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("flags", C.c_uint32), ("min_history", C.c_int)]
@@ -1062,6 +1088,16 @@ class RayTracerScene:
         self.commit()
         params = params if params is not None else OcclusionParams()
         _check(library().rtw_render_occlusion(self.h, features.h, C.byref(params), int(first_pass), int(n_passes), C.c_uint32(seed), dst.h))
+
+    def render_lighting(self, features, dst, lights, params=None, first_pass=0, n_passes=1, seed=12345):
+        """rtw_render_lighting: direct light of up to 8 Lights on what the FeatureBuffers show under the current camera -- per light the cosine times the
+        unoccluded share of params.samples shadow rays -- the passes accumulated into the Framebuffer dst like render passes (the formula is
+        include/rtwin.h's).  Asynchronous on the context's stream, one launch."""
+        self.commit()
+        params = params if params is not None else LightingParams()
+        lights = list(lights)
+        arr = (Light * max(len(lights), 1))(*lights)
+        _check(library().rtw_render_lighting(self.h, features.h, arr, len(lights), C.byref(params), int(first_pass), int(n_passes), C.c_uint32(seed), dst.h))
 
     def render_reserve(self, fb, task_rows, rank, world, MaxBounceCount, n_passes, sub_samples=4):
         """rtw_render_reserve: bins, tile tables and workspace of a later render_passes call with these arguments (renders nothing)"""

@@ -215,6 +215,30 @@ struct OcclusionCall {
 bool occlusion_is_by_sample(int order);
 void occlusion_launch_shape(const OcclusionCall& o, int* threads, unsigned* blocks, int* staged_top, bool* staged_all);
 int launch_occlusion(const RtwSceneDev* sc, const OcclusionCall& o, hipStream_t stream);
+// ---- direct lighting from the feature buffers (rtw_lighting_kernels.h): one launch on `stream`, no workspace; the lights travel in the launch's arguments ----
+constexpr uint32_t LIGHTING_ALBEDO = 1u;        // == RTW_LIGHTING_ALBEDO of rtwin.h
+struct LightingCall {
+    const void *geom, *albedo, *ids;            // the features (never written)
+    void *accum, *argb;                         // the destination: accumulated into
+    const float* gamma_thr;
+    RtwCamera cam;
+    int width, height;
+    RtwLight lights[RTW_LT_MAX];
+    int n_lights;                               // 1..RTW_LT_MAX
+    float bias;
+    int samples;                                // 1..RTW_LT_MAX
+    uint32_t flags;
+    int first_pass, n_passes;
+    uint32_t seed;
+    int deal;                                   // 0 = positional, 1 = compacted, -1 = the measured rule (lighting_is_compacted)
+    int cu_count = 256;
+    bool single_mesh = false;                   // as QueryTuning's
+    int staged_shape = -1, staged_top = 0;
+    bool staged_all = false;
+};
+bool lighting_is_compacted(int deal);
+void lighting_launch_shape(const LightingCall& o, int* threads, unsigned* blocks, int* staged_top, bool* staged_all);
+int launch_lighting(const RtwSceneDev* sc, const LightingCall& o, hipStream_t stream);
 // ---- the HDR display transform (rtw_tonemap_kernels.h): histogram metering, exposure, tone curve and pack in one launch on `stream`, no workspace ----
 constexpr int TONEMAP_LINEAR = 0, TONEMAP_REINHARD = 1, TONEMAP_ACES = 2;      // == RTW_TONEMAP_* of rtwin.h
 constexpr int TONEMAP_BIN0 = 856;               // bin = (float bits >> 20) - 856: 8 bins per octave from 2^-20

@@ -91,6 +91,8 @@ typedef __attribute__((address_space(3))) const float4 rtw_l_f4;
 __device__ __forceinline__ float4 lld4(const float4* p, int i) { return ((rtw_l_f4*)p)[i]; }
 __device__ __forceinline__ uint32_t lldu(const uint32_t* p, int i) { return ((rtw_l_u1*)p)[i]; }
 __device__ __forceinline__ void lstu(uint32_t* p, int i, uint32_t v) { ((rtw_l_u1w*)p)[i] = v; }
+// bits into an LDS word several waves set bits of: an integer, so the word does not depend on who came first
+__device__ __forceinline__ void lds_or(uint32_t* p, int i, uint32_t v) { (void)__hip_atomic_fetch_or((rtw_l_u1w*)p + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 #else
 __device__ __forceinline__ float4 cld4(const float4* p, int i) { return p[i]; }
 __device__ __forceinline__ uint32_t cldu(const uint32_t* p, int i) { return p[i]; }
@@ -100,6 +102,7 @@ __device__ __forceinline__ float lld1(const float* p, int i) { return p[i]; }
 __device__ __forceinline__ float4 lld4(const float4* p, int i) { return p[i]; }
 __device__ __forceinline__ uint32_t lldu(const uint32_t* p, int i) { return p[i]; }
 __device__ __forceinline__ void lstu(uint32_t* p, int i, uint32_t v) { p[i] = v; }
+__device__ __forceinline__ void lds_or(uint32_t* p, int i, uint32_t v) { p[i] |= v; }
 #endif
 
 struct Ray { f3 o, d; float dist; };
@@ -1123,6 +1126,7 @@ __global__ __launch_bounds__(256, 3) void shade_kernel(const RtwSceneDev* __rest
 #include "rtw_budget_kernels.h"
 #include "rtw_query_kernels.h"
 #include "rtw_occlusion_kernels.h"
+#include "rtw_lighting_kernels.h"
 #include "rtw_tonemap_kernels.h"
 #include "rtw_build_kernels.h"
 
@@ -2098,6 +2102,54 @@ int launch_tonemap(const TonemapCall& c, hipStream_t stream)
 int launch_exposure_state(uint32_t* state, float exposure, bool metered, bool clear, hipStream_t stream)
 {
     launch(exposure_state_kernel, dim3(1), dim3(256), 0, stream, state, exposure, metered ? 1u : 0u, clear ? 1 : 0);
+    return (int)hipGetLastError();
+}
+
+// ---- direct lighting from the feature buffers (rtw_lighting_kernels.h) ---------------------------------------------------------------------
+// "lighting_deal" -1, as measured with tools/lighting_bench.py at 1080p, 1 light x 1 sample and 4 x 4 (profiles/lighting_experiments.md): the compacted
+// deal is ahead by more than both spreads in one of four configurations (the default scene, 1 x 1, an eighth of the jobs alive) and behind in two, and
+// the host does not know the share of live jobs, so: positional
+bool lighting_is_compacted(int deal) { return deal < 0 ? false : deal != 0; }
+
+// The block shape of a call, by the occlusion call's rule: a staged block's LDS is its candidate lists, the block's pixel, mask and queue words and as
+// many of the tree's upper records as the rest of 128 KiB holds
+void lighting_launch_shape(const LightingCall& o, int* threads, unsigned* blocks, int* staged_top, bool* staged_all)
+{
+    const long long tiles = (long long)((o.width + LT_TILE - 1) / LT_TILE) * (long long)((o.height + LT_TILE - 1) / LT_TILE);
+    const long long room = (131072 - (long long)RTW_GT_CAP_STAGED * 1024 * 4 - (long long)lt_block_words(1024, lighting_is_compacted(o.deal)) * 4) / 32;
+    int top = o.staged_shape >= 0 ? o.staged_top : 0;
+    if (top > room) top = (int)room;
+    const bool staged = top >= 64;
+    *staged_top = staged ? top : 0; *staged_all = staged && o.staged_all && top == o.staged_top;
+    const int nt = staged ? 1024 : 256;
+    long long most = (long long)o.cu_count * (staged ? 1 : 8);
+    const long long need = (tiles + nt / 256 - 1) / (nt / 256);
+    if (most > need) most = need;
+    if (most < 1) most = 1;
+    *threads = nt; *blocks = (unsigned)most;
+}
+
+int launch_lighting(const RtwSceneDev* sc, const LightingCall& o, hipStream_t stream)
+{
+    if (o.width < 1 || o.height < 1 || o.samples < 1 || o.samples > RTW_LT_MAX || o.n_lights < 1 || o.n_lights > RTW_LT_MAX || o.n_passes < 1) return (int)hipErrorInvalidValue;
+    LightingBufs b;
+    b.geom = (const float4*)o.geom; b.albedo = (const float4*)o.albedo; b.ids = (const unsigned long long*)o.ids;
+    b.accum = (float4*)o.accum; b.argb = (uint32_t*)o.argb; b.gamma_thr = o.gamma_thr; b.cam = o.cam;
+    b.width = o.width; b.height = o.height; b.tiles_x = (o.width + LT_TILE - 1) / LT_TILE; b.n_tiles = b.tiles_x * ((o.height + LT_TILE - 1) / LT_TILE);
+    b.bias = o.bias; b.samples = o.samples; b.n_lights = o.n_lights; b.use_albedo = (o.flags & LIGHTING_ALBEDO) ? 1 : 0;
+    b.first_pass = o.first_pass; b.n_passes = o.n_passes; b.seed = o.seed;
+    std::memset(b.lights, 0, sizeof b.lights);
+    for (int j = 0; j < o.n_lights; j++) b.lights[j] = o.lights[j];
+    int nt, top; unsigned blocks; bool all;
+    lighting_launch_shape(o, &nt, &blocks, &top, &all);
+    const bool compact = lighting_is_compacted(o.deal);
+    with_trace_shape(nt == 1024, all, [&](auto SH) {
+        using S = decltype(SH);
+        const size_t lds = S::lds(top) + (size_t)lt_block_words(S::NT, compact) * 4;
+        with_flags(!o.single_mesh, compact, [&](auto AN, auto CO) {
+            launch(lighting_kernel<decltype(AN)::value, S::NT, S::CAP, S::STG, decltype(CO)::value>, dim3(blocks), dim3(S::NT), lds, stream, sc, b, o.staged_shape, top);
+        });
+    });
     return (int)hipGetLastError();
 }
 

@@ -169,6 +169,36 @@ RTW_HD float occlusion_weight(f3 n, f3 d, bool cosine)
     return dt > 0.0f ? dt : 0.0f;
 }
 
+// ---- direct lighting from the feature buffers (rtw_render_lighting of rtwin.h, steps 2 to 5; step 1 is occlusion_origin) -----------------------------
+// Every product and every sum rounded on its own, in the order written; the tests' NumPy model repeats them.
+// the unit-table entry that moves light j for sample s of pass k of a pixel: draw j of the sample's own stream, modulo the table size (as above)
+RTW_HD uint32_t lighting_table_index(uint32_t seed, uint32_t pixel, uint32_t pass, uint32_t s, uint32_t j)
+{
+    const uint32_t x = stream_draw31(stream_key(seed, pixel, (pass * 64u + s) | RTW_LIGHTING_STREAM), j);
+    uint32_t i = (x & 0xFFFFFFu) + (x >> 24);
+    if (i >= RTW_TABLE_SIZE) i -= RTW_TABLE_SIZE;
+    return i;
+}
+// The shadow ray (O, d, dist) from the origin O of a pixel with unit normal n towards light L moved by the table entry u (zero for radius 0), and
+// t = c * att, what the sample adds when nothing stands between.  false: no ray exists -- the light is behind the surface, at it, or not a number --
+// and t = 0
+RTW_HD bool lighting_ray(const RtwLight& L, f3 u, f3 O, f3 n, f3& d, float& dist, float& t)
+{
+    const f3 D0 = mk(L.v[0] + u.x * L.radius, L.v[1] + u.y * L.radius, L.v[2] + u.z * L.radius);
+    const f3 D = L.type == RTW_LT_POINT ? D0 - O : D0;
+    const float len = sqrtf(dot(D, D));
+    const float inv = 1.0f / len;
+    d = mk(D.x * inv, D.y * inv, D.z * inv);
+    dist = L.type == RTW_LT_POINT ? len : 1000.0f;
+    t = 0.0f;
+    if (L.type == RTW_LT_POINT && !(len > 0.0f && len <= FLT_MAX)) return false;
+    const float att = (L.flags & RTW_LT_INVERSE_SQUARE) ? 1.0f / (len * len) : 1.0f;
+    const float c = dot(n, d);
+    if (!(c > 0.0f)) return false;
+    t = c * att;
+    return true;
+}
+
 // ---- guided upsampling (rtw_upsample of rtwin.h, step 1) ------------------------------------------------------------------------------
 // Pixel x of a `size`-wide frame looks through the screen point (x - size / 2) / size (pixel_dx without its sign and scale); in a `low`-wide frame
 // of the same camera that point lies tx of the way from pixel x0 to pixel x0 + 1.  Integers up to the last division: n = (x - size / 2) * low,

@@ -183,6 +183,15 @@ struct RtwRenderParams {
 #define RTW_LENS_STREAM 0x80000000u
 // an occlusion sample's random stream (rtw_render_occlusion of rtwin.h): stream_key(seed, pixel, (pass * 64 + sample) | RTW_OCCLUSION_STREAM), pass < 2^24
 #define RTW_OCCLUSION_STREAM 0x40000000u
+// a shadow sample's random stream (rtw_render_lighting of rtwin.h): stream_key(seed, pixel, (pass * 64 + sample) | RTW_LIGHTING_STREAM), pass < 2^24; both
+// tag bits, so no value of it is a path's (< 2^26), a lens point's (bit 30 clear) or an occlusion sample's (bit 31 clear)
+#define RTW_LIGHTING_STREAM 0xC0000000u
+// rtw_light of rtwin.h, field for field (9 words): type 0 = point (v a position), 1 = directional (v the unit direction towards the light)
+struct RtwLight { int32_t type; uint32_t flags; float v[3]; float color[3]; float radius; };
+#define RTW_LT_POINT 0
+#define RTW_LT_DIRECTIONAL 1
+#define RTW_LT_INVERSE_SQUARE 1u
+#define RTW_LT_MAX 8            // lights of a call, and samples per light and pass: a pixel's jobs of one pass fill a 64-bit mask
 
 // screen-space bins of one shape for one (width, height, tile shape): CSR over the bins, entries = node index of a leaf, ascending
 struct RtwBinsDev {
