@@ -331,6 +331,9 @@ inline Light MakeLight(int Type, const RVec3& PositionOrDirection, const RVec3& 
     l.color[0] = Color.x; l.color[1] = Color.y; l.color[2] = Color.z;
     return l;
 }
+// rtw_indirect_params (bias 1e-3, 4 gather rays per pass, albedo on) for RayTracerScene::RenderIndirect
+typedef rtw_indirect_params IndirectParams;
+inline IndirectParams IndirectDefaults() { IndirectParams p; RtwCheck(rtw_indirect_default_params(&p)); return p; }
 // The display transform's metering state on the device (rtw_exposure of rtwin.h): the exposure Tonemap maps the next frame with, adapted by every
 // metering call from the frame's log-luminance histogram
 class Exposure {
@@ -456,6 +459,13 @@ public:
     {
         Commit();
         RtwCheck(rtw_render_lighting(Scene, Features.Get(), Lights.data(), (int)Lights.size(), &Params, FirstPass, NumPasses, Seed, Destination.Get()));
+    }
+    // One bounce of indirect light on what Features show: Params.samples gather rays per pixel and pass, each hit lit by Lights (none: the sky alone)
+    // with one shadow ray per light, accumulated into Destination like render passes.  Asynchronous, one launch: rtw_render_indirect
+    void RenderIndirect(FeatureBuffers& Features, const std::vector<Light>& Lights, const IndirectParams& Params, int FirstPass, int NumPasses, uint32_t Seed, ColorBuffer& Destination)
+    {
+        Commit();
+        RtwCheck(rtw_render_indirect(Scene, Features.Get(), Lights.empty() ? nullptr : Lights.data(), (int)Lights.size(), &Params, FirstPass, NumPasses, Seed, Destination.Get()));
     }
     void Commit() { if (!Committed) { RtwCheck(rtw_scene_commit(Scene)); Committed = true; } }
     rtw_scene* Get() { Commit(); return Scene; }

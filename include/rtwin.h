@@ -641,6 +641,48 @@ typedef struct rtw_lighting_params { float bias; int samples; uint32_t flags; } 
 int rtw_lighting_default_params(rtw_lighting_params* p);
 int rtw_render_lighting(rtw_scene* scene, rtw_features* f, const rtw_light* lights, int n_lights, const rtw_lighting_params* p, int first_pass, int n_passes, uint32_t seed, rtw_framebuffer* dst);
 
+/* ---- one bounce of indirect light from the feature buffers: what the first hit's neighbourhood, lit by the same lights, sends back to it (no reference
+ * counterpart: its path tracer never sees the lights, USE_LIGHTS 0) ----
+ * From each pixel's first hit `samples` gather rays go into the scene; the point a ray meets is shaded with the lights and one shadow ray per light, and the
+ * radiance comes back weighted by the cosine.  The calls compose by addition: path-traced frame + rtw_render_lighting + rtw_render_indirect.  The frame is
+ * W x H, shared by f and dst, in the scene's context; the camera is the scene's current camera.  Everything is float32, every product, sum and quotient
+ * rounded on its own, in the order written.
+ *  1 pixel states    EMPTY / OPEN / CAST, n, P and O = P + n * bias: rtw_render_occlusion's steps 1 to 3.  An EMPTY pixel is not written.  An OPEN pixel takes
+ *                    e = (0, 0, 0) in every pass, and its count still grows: the sky has no indirect term, so direct + indirect does not count the sky twice.
+ *  2 gather ray      for pass k and sample s = 0 .. samples - 1 the direction d is exactly the occlusion ray's: the same key (k * 64 + s) |
+ *                    RTW_OCCLUSION_STREAM (0x40000000), draw 0, table entry, flipped into n's hemisphere.  c_s = dot(n, d).  The ray is (O, d, 1000).  With
+ *                    RTW_INDIRECT_MIRROR d = reflect(w, n) = w - (n * 2) * dot(w, n) instead, w the unit direction of the pixel's pinhole ray; if
+ *                    dot(d, n) > 0 is false then, no ray exists and L_s = 0, c_s = 0.
+ *  3 gather hit      the closest hit as rtw_trace_closest reports it: shape, position X, normal m.  A miss: L_s is the sky colour of d and no shadow ray is
+ *                    cast.  A hit: a_s is the preview colour of that ray, exactly what rtw_render_features records as one sample's albedo (UseBaseColor,
+ *                    texel inheritance included, 0 for a shape without material); a Blend in the preview draws from the path stream of step 2's key with its
+ *                    counter starting at 1.  O2 = X + m * bias.
+ *  4 light jobs      for light j = 0 .. n_lights - 1: rtw_render_lighting's steps 2 to 6 with (O2, m) in place of (O, n), sample index s and counter j of
+ *                    the lighting stream, one shadow ray per light: t_j.  E_s = sum_j color_j * t_j, in light order, from +0.  L_s = a_s * E_s per channel.
+ *  5 per pass        A = sum_s L_s * c_s per channel, Wt = sum_s c_s, both summed left to right from +0.  g = Wt > 0 ? A / Wt : 0.  With
+ *                    RTW_INDIRECT_ALBEDO e = g * (albedo.xyz / cf), otherwise e = g.
+ *  6 accumulation    rtw_render_lighting's step 9: dst.accum.xyz += e, count += 1 per pass, the ARGB pack after the call's last pass.
+ * The result depends on the scene, the camera, f, the lights, the parameters, the passes and the seed only.  The context option "indirect_deal" (-1) picks how
+ * the light jobs of step 4 are dealt to the lanes -- 0 = positional: a job sits where its gather ray sat, a dead one idles through the walk; 1 = compacted: the
+ * jobs that survive a miss and the cosine test are queued and walked 64 at a time; -1 = the faster by measurement -- and never changes a bit.  -1 means 1
+ * from two light jobs a pixel and pass on (samples x n_lights >= 2) and 0 for one: two sessions on an MI355X measured 1 x 1, 4 x 2 and 8 x 8 samples x
+ * lights on two scenes with the default blocks and with the staging blocks below (profiles/indirect_experiments.md).  "indirect_staging" (-1) 1 = 512-thread blocks with a tree's upper levels in LDS where the scene has one to stage, 0 = 256-thread blocks,
+ * -1 = by the same sessions 0; it never changes a bit either.
+ * Limits: n_lights 0..8, and `lights` may be null when it is 0 (that case gathers the sky alone); samples 1..8; the scene as committed; under a lens the
+ * surface point is the pinhole's; emission is not gathered (emitters belong to the path tracer), and an emissive leaf's preview colour is treated like any
+ * other preview colour.
+ * `lights` is host memory, copied into the launch's arguments.  f is not written.  Asynchronous on the context's stream: ONE launch whatever n_passes is (a
+ * pixel's accumulator entry is read once and written once), no work space, no allocation, copy or synchronisation; no ray is stored to memory.  The work
+ * counters (rtw_stats) do not count these rays.
+ * RTW_ERR_STATE: the scene is not committed.  RTW_ERR_INVALID, with dst untouched: everything rtw_render_lighting refuses, with n_lights outside 0..8
+ * (lights null with n_lights > 0) and samples outside 1..8; unknown flag bits. */
+#define RTW_INDIRECT_ALBEDO 1u
+#define RTW_INDIRECT_MIRROR 2u
+typedef struct rtw_indirect_params { float bias; int samples; uint32_t flags; } rtw_indirect_params;
+/* bias 1e-3, samples 4, flags RTW_INDIRECT_ALBEDO */
+int rtw_indirect_default_params(rtw_indirect_params* p);
+int rtw_render_indirect(rtw_scene* scene, rtw_features* f, const rtw_light* lights, int n_lights, const rtw_indirect_params* p, int first_pass, int n_passes, uint32_t seed, rtw_framebuffer* dst);
+
 /* ---- HDR display transform: histogram auto-exposure, a tone curve and the ARGB pack (no reference counterpart: its resolve divides, clamps and packs) ----
  * The chain hands over linear radiance -- emitters, mirror paths onto emitters -- that a clamp to [0, 1] turns white, and a moving camera wants an
  * exposure that follows the frame.  rtw_tonemap meters src with a log-luminance histogram, adapts the exposure of the rtw_exposure object, maps src with

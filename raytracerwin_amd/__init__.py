@@ -9,7 +9,7 @@ interface for that path, over ctypes: same names, same argument meaning
 fallback: without the built library or without a GPU every device call raises.
 """
 from .api import (  # noqa: F401
-    Camera, Comm, Context, DenoiseParams, DenoiseVarianceParams, Exposure, FeatureBuffers, Framebuffer, Lens, Light, LightingParams, Moments, OcclusionParams, RayTracerScene, ReprojectParams, SampleBudgetParams, TonemapParams, UpsampleParams, camera_rays, denoise, denoise_variance, lens_rays, meter_exposure, reproject, reproject_moments, sample_budget, tonemap, upsample, RCapsule, RMeshShape, RPlane, RSphere, RTriangle, RenderOption, RtwError,
+    Camera, Comm, Context, DenoiseParams, DenoiseVarianceParams, Exposure, FeatureBuffers, Framebuffer, IndirectParams, Lens, Light, LightingParams, Moments, OcclusionParams, RayTracerScene, ReprojectParams, SampleBudgetParams, TonemapParams, UpsampleParams, camera_rays, denoise, denoise_variance, lens_rays, meter_exposure, reproject, reproject_moments, sample_budget, tonemap, upsample, RCapsule, RMeshShape, RPlane, RSphere, RTriangle, RenderOption, RtwError,
     SurfaceMaterial_Blend, SurfaceMaterial_Combine, SurfaceMaterial_Diffuse, SurfaceMaterial_DiffuseChecker,
     SurfaceMaterial_Emissive, SurfaceMaterial_Null, SurfaceMaterial_Reflective,
     MATERIAL_CLASS_FLAT, MATERIAL_CLASS_FLAT_TEX, MATERIAL_CLASS_GENERAL,

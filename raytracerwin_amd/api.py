@@ -742,6 +742,18 @@ class LightingParams(C.Structure):
             setattr(self, k, v)
 
 
+class IndirectParams(C.Structure):
+    """rtw_indirect_params; IndirectParams() holds rtw_indirect_default_params' values (1e-3, 4, ALBEDO), keywords override them"""
+    _fields_ = [("bias", C.c_float), ("samples", C.c_int), ("flags", C.c_uint32)]
+    ALBEDO, MIRROR = 1, 2
+
+    def __init__(self, **kw):
+        super().__init__()
+        _check(library().rtw_indirect_default_params(C.byref(self)))
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
 class DenoiseVarianceParams(C.Structure):
     """rtw_denoise_variance_params; DenoiseVarianceParams() holds rtw_denoise_variance_default_params' values (5, 4.0, 0.3, 0.1, both flags, 4)"""
     _fields_ = [("levels", C.c_int), ("sigma_lum", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("flags", C.c_uint32), ("min_history", C.c_int)]
@@ -1098,6 +1110,16 @@ class RayTracerScene:
         lights = list(lights)
         arr = (Light * max(len(lights), 1))(*lights)
         _check(library().rtw_render_lighting(self.h, features.h, arr, len(lights), C.byref(params), int(first_pass), int(n_passes), C.c_uint32(seed), dst.h))
+
+    def render_indirect(self, features, dst, lights=(), params=None, first_pass=0, n_passes=1, seed=12345):
+        """rtw_render_indirect: one bounce of indirect light on what the FeatureBuffers show -- params.samples gather rays per pixel and pass, each hit
+        lit by up to 8 Lights (none: the sky alone) with one shadow ray per light -- the passes accumulated into the Framebuffer dst like render passes
+        (the formula is include/rtwin.h's).  Asynchronous on the context's stream, one launch."""
+        self.commit()
+        params = params if params is not None else IndirectParams()
+        lights = list(lights)
+        arr = (Light * len(lights))(*lights) if lights else None
+        _check(library().rtw_render_indirect(self.h, features.h, arr, len(lights), C.byref(params), int(first_pass), int(n_passes), C.c_uint32(seed), dst.h))
 
     def render_reserve(self, fb, task_rows, rank, world, MaxBounceCount, n_passes, sub_samples=4):
         """rtw_render_reserve: bins, tile tables and workspace of a later render_passes call with these arguments (renders nothing)"""

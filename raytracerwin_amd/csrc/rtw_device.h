@@ -239,6 +239,32 @@ struct LightingCall {
 bool lighting_is_compacted(int deal);
 void lighting_launch_shape(const LightingCall& o, int* threads, unsigned* blocks, int* staged_top, bool* staged_all);
 int launch_lighting(const RtwSceneDev* sc, const LightingCall& o, hipStream_t stream);
+// ---- one bounce of indirect light from the feature buffers (rtw_indirect_kernels.h): one launch on `stream`, no workspace ----
+constexpr uint32_t INDIRECT_ALBEDO = 1u, INDIRECT_MIRROR = 2u;     // == RTW_INDIRECT_* of rtwin.h
+struct IndirectCall {
+    const void *geom, *albedo, *ids;            // the features (never written)
+    void *accum, *argb;                         // the destination: accumulated into
+    const float* gamma_thr;
+    RtwCamera cam;
+    int width, height;
+    RtwLight lights[RTW_LT_MAX];
+    int n_lights;                               // 0..RTW_LT_MAX
+    float bias;
+    int samples;                                // 1..RTW_LT_MAX
+    uint32_t flags;
+    int first_pass, n_passes;
+    uint32_t seed;
+    int deal;                                   // 0 = positional, 1 = compacted, -1 = the rule (indirect_is_compacted)
+    int staging = -1;                           // 1 = staging blocks of 512 threads, 0 = nothing staged (256-thread blocks), -1 = the rule (indirect_is_staged)
+    int cu_count = 256;
+    bool single_mesh = false, carry = false;    // as QueryTuning's
+    int staged_shape = -1, staged_top = 0;
+    bool staged_all = false;
+};
+bool indirect_is_compacted(int deal, int samples, int n_lights);
+bool indirect_is_staged(int staging);
+void indirect_launch_shape(const IndirectCall& o, int* threads, unsigned* blocks, int* staged_top, bool* staged_all);
+int launch_indirect(const RtwSceneDev* sc, const IndirectCall& o, hipStream_t stream);
 // ---- the HDR display transform (rtw_tonemap_kernels.h): histogram metering, exposure, tone curve and pack in one launch on `stream`, no workspace ----
 constexpr int TONEMAP_LINEAR = 0, TONEMAP_REINHARD = 1, TONEMAP_ACES = 2;      // == RTW_TONEMAP_* of rtwin.h
 constexpr int TONEMAP_BIN0 = 856;               // bin = (float bits >> 20) - 856: 8 bins per octave from 2^-20

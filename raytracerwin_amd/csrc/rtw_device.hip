@@ -1127,6 +1127,7 @@ __global__ __launch_bounds__(256, 3) void shade_kernel(const RtwSceneDev* __rest
 #include "rtw_query_kernels.h"
 #include "rtw_occlusion_kernels.h"
 #include "rtw_lighting_kernels.h"
+#include "rtw_indirect_kernels.h"
 #include "rtw_tonemap_kernels.h"
 #include "rtw_build_kernels.h"
 
@@ -2149,6 +2150,61 @@ int launch_lighting(const RtwSceneDev* sc, const LightingCall& o, hipStream_t st
         with_flags(!o.single_mesh, compact, [&](auto AN, auto CO) {
             launch(lighting_kernel<decltype(AN)::value, S::NT, S::CAP, S::STG, decltype(CO)::value>, dim3(blocks), dim3(S::NT), lds, stream, sc, b, o.staged_shape, top);
         });
+    });
+    return (int)hipGetLastError();
+}
+
+// ---- one bounce of indirect light from the feature buffers (rtw_indirect_kernels.h) -------------------------------------------------------------
+// "indirect_deal" -1, as tools/indirect_bench.py measured it at 1080p, 1 x 1, 4 x 2 and 8 x 8 samples x lights, on TorusKnot and on the default scene
+// (profiles/indirect_experiments.md, sessions B and C): with staging blocks the compacted deal is ahead by more than both spreads at 4 x 2 and 8 x 8 on
+// both scenes and level at 1 x 1; with the default blocks it is level with them at 4 x 2, ahead of them at 8 x 8, and at 1 x 1 -- one light job a pixel and
+// pass -- behind the positional deal of session B by 30 % on TorusKnot and level on the default scene.  So: compacted from two light jobs a pixel on
+bool indirect_is_compacted(int deal, int samples, int n_lights) { return deal < 0 ? samples * n_lights >= 2 : deal != 0; }
+// "indirect_staging" -1, same sessions: against 256-thread blocks with nothing staged the 512-thread staging blocks are 14 to 16 % behind at 1 x 1, level at
+// 4 x 2, and at 8 x 8 5 % ahead under the positional deal and 2 to 12 % behind under the compacted one, on both scenes.  So: not staged
+bool indirect_is_staged(int staging) { return staging > 0; }
+
+// The block shape of a call.  The kernel holds the closest-hit walk, the finish and the any-hit walk: under __launch_bounds__(1024) it spills VGPRs,
+// so a staged block is IN_STAGED_NT = 512 threads (256 VGPRs a lane, no spill): its LDS is its candidate lists, the block's pixel, mask, hit, record
+// and queue words and as many of the tree's upper records as the rest of 128 KiB holds, one block a CU.  "indirect_staging" 0 never stages.
+// Nothing staged: 256 threads, 4 blocks a CU -- what 122 to 139 VGPRs allow at most; the 4 itself has not been measured against 3 or 8
+void indirect_launch_shape(const IndirectCall& o, int* threads, unsigned* blocks, int* staged_top, bool* staged_all)
+{
+    const long long tiles = (long long)((o.width + LT_TILE - 1) / LT_TILE) * (long long)((o.height + LT_TILE - 1) / LT_TILE);
+    const long long room = (131072 - (long long)RTW_GT_CAP_STAGED * IN_STAGED_NT * 4 - (long long)in_block_words(IN_STAGED_NT, o.samples, indirect_is_compacted(o.deal, o.samples, o.n_lights)) * 4) / 32;
+    int top = o.staged_shape >= 0 && indirect_is_staged(o.staging) ? o.staged_top : 0;
+    if (top > room) top = (int)room;
+    const bool staged = top >= 64;
+    *staged_top = staged ? top : 0; *staged_all = staged && o.staged_all && top == o.staged_top;
+    const int nt = staged ? IN_STAGED_NT : 256;
+    long long most = (long long)o.cu_count * (staged ? 1 : 4);
+    const long long need = (tiles + nt / 256 - 1) / (nt / 256);
+    if (most > need) most = need;
+    if (most < 1) most = 1;
+    *threads = nt; *blocks = (unsigned)most;
+}
+
+int launch_indirect(const RtwSceneDev* sc, const IndirectCall& o, hipStream_t stream)
+{
+    if (o.width < 1 || o.height < 1 || o.samples < 1 || o.samples > RTW_LT_MAX || o.n_lights < 0 || o.n_lights > RTW_LT_MAX || o.n_passes < 1) return (int)hipErrorInvalidValue;
+    IndirectBufs b;
+    b.geom = (const float4*)o.geom; b.albedo = (const float4*)o.albedo; b.ids = (const unsigned long long*)o.ids;
+    b.accum = (float4*)o.accum; b.argb = (uint32_t*)o.argb; b.gamma_thr = o.gamma_thr; b.cam = o.cam;
+    b.width = o.width; b.height = o.height; b.tiles_x = (o.width + LT_TILE - 1) / LT_TILE; b.n_tiles = b.tiles_x * ((o.height + LT_TILE - 1) / LT_TILE);
+    b.bias = o.bias; b.samples = o.samples; b.n_lights = o.n_lights;
+    b.use_albedo = (o.flags & INDIRECT_ALBEDO) ? 1 : 0; b.mirror = (o.flags & INDIRECT_MIRROR) ? 1 : 0; b.carry_on = o.carry ? 1 : 0;
+    b.first_pass = o.first_pass; b.n_passes = o.n_passes; b.seed = o.seed;
+    std::memset(b.lights, 0, sizeof b.lights);
+    for (int j = 0; j < o.n_lights; j++) b.lights[j] = o.lights[j];
+    int nt, top; unsigned blocks; bool all;
+    indirect_launch_shape(o, &nt, &blocks, &top, &all);
+    const bool compact = indirect_is_compacted(o.deal, o.samples, o.n_lights);
+    const size_t words = (size_t)in_block_words(nt, o.samples, compact) * 4;
+    with_flags(!o.single_mesh, compact, all, [&](auto AN, auto CO, auto ALL) {
+        constexpr bool an = decltype(AN)::value, co = decltype(CO)::value;
+        if (nt == 256) launch(indirect_kernel<an, 256, RTW_GT_CAP, 0, co>, dim3(blocks), dim3(256), (size_t)RTW_GT_CAP * 256 * 4 + words, stream, sc, b, o.staged_shape, 0);
+        else launch(indirect_kernel<an, IN_STAGED_NT, RTW_GT_CAP_STAGED, decltype(ALL)::value ? 2 : 1, co>, dim3(blocks), dim3(IN_STAGED_NT),
+                    (size_t)RTW_GT_CAP_STAGED * IN_STAGED_NT * 4 + words + (size_t)top * 32, stream, sc, b, o.staged_shape, top);
     });
     return (int)hipGetLastError();
 }

@@ -199,6 +199,26 @@ RTW_HD bool lighting_ray(const RtwLight& L, f3 u, f3 O, f3 n, f3& d, float& dist
     return true;
 }
 
+// ---- one bounce of indirect light from the feature buffers (rtw_render_indirect of rtwin.h, step 2; step 1 is occlusion_origin, the table entry
+// occlusion_table_index's, step 4 lighting_table_index and lighting_ray at the gather hit) --------------------------------------------------------
+// the unit direction of the pinhole ray of pixel (x, y): the one reproject_point walks along
+RTW_HD f3 pinhole_direction(const RtwCamera& c, int x, int y, int width, int height)
+{
+    const f3 v = camera_view(c, pixel_dx(x, width, frame_aspect(width, height)), pixel_dy(y, height));
+    const float inv = 1.0f / sqrtf(dot(v, v));
+    return mk(v.x * inv, v.y * inv, v.z * inv);
+}
+// The gather direction d and its weight c = dot(n, d): the occlusion ray's direction from the table entry v, or with `mirror` the pinhole direction w
+// reflected at n (Src/RVector.h:218).  false: a mirror direction that does not leave the surface -- no ray exists, c = 0
+RTW_HD bool indirect_ray(f3 v, f3 w, f3 n, bool mirror, f3& d, float& c)
+{
+    if (mirror) { const float dt = dot(w, n); d = mk(w.x - (n.x * 2.0f) * dt, w.y - (n.y * 2.0f) * dt, w.z - (n.z * 2.0f) * dt); }
+    else d = occlusion_direction(v, n);
+    c = dot(n, d);
+    if (mirror && !(c > 0.0f)) { c = 0.0f; return false; }
+    return true;
+}
+
 // ---- guided upsampling (rtw_upsample of rtwin.h, step 1) ------------------------------------------------------------------------------
 // Pixel x of a `size`-wide frame looks through the screen point (x - size / 2) / size (pixel_dx without its sign and scale); in a `low`-wide frame
 // of the same camera that point lies tx of the way from pixel x0 to pixel x0 + 1.  Integers up to the last division: n = (x - size / 2) * low,

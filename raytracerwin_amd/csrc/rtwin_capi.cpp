@@ -163,6 +163,8 @@ struct rtw_context {
     int upsample_staging = -1;          // option: rtw_upsample's taps: 0 = from global memory, 1 = the tile's box of low-resolution records staged in LDS, -1 = the measured rule (rtw::upsample_is_staged); same bits either way
     int occlusion_order = -1;           // option: rtw_render_occlusion's ray order: 0 = a lane per pixel, 1 = a lane per sample, -1 = the measured rule (rtw::occlusion_is_by_sample); same bits either way
     int lighting_deal = -1;             // option: rtw_render_lighting's work split: 0 = positional (a lane per pixel, culled jobs idle), 1 = compacted (a queue of the surviving jobs), -1 = the measured rule (rtw::lighting_is_compacted); same bits either way
+    int indirect_deal = -1;             // option: rtw_render_indirect's deal of the light jobs at the gather hits: 0 = positional, 1 = compacted (a queue of the surviving jobs), -1 = the rule (rtw::indirect_is_compacted); same bits either way
+    int indirect_staging = -1;          // option: rtw_render_indirect's blocks: 1 = 512 threads with a tree's upper levels in LDS where there is one, 0 = 256 threads, nothing staged, -1 = the measured rule (rtw::indirect_is_staged); same bits either way
     int tonemap_histogram = -1;         // option: rtw_tonemap's histogram in LDS: 0 = an atomic per lane, 1 = wave-aggregated, -1 = the measured rule (rtw::tonemap_histogram_is_aggregated); same bits either way
     int tonemap_blocks = 0;             // option: > 0 = rtw_tonemap launches at most this many blocks (few pixels then make many trips of its chunk loop)
 };
@@ -399,6 +401,8 @@ int rtw_context_set_option(rtw_context* ctx, const char* name, int value)
     if (std::strcmp(name, "upsample_staging") == 0) { ctx->upsample_staging = value < 0 ? -1 : (value ? 1 : 0); return RTW_OK; }
     if (std::strcmp(name, "occlusion_order") == 0) { ctx->occlusion_order = value < 0 ? -1 : (value ? 1 : 0); return RTW_OK; }
     if (std::strcmp(name, "lighting_deal") == 0) { ctx->lighting_deal = value < 0 ? -1 : (value ? 1 : 0); return RTW_OK; }
+    if (std::strcmp(name, "indirect_deal") == 0) { ctx->indirect_deal = value < 0 ? -1 : (value ? 1 : 0); return RTW_OK; }
+    if (std::strcmp(name, "indirect_staging") == 0) { ctx->indirect_staging = value < 0 ? -1 : (value ? 1 : 0); return RTW_OK; }
     if (std::strcmp(name, "tonemap_histogram") == 0) { ctx->tonemap_histogram = value < 0 ? -1 : (value ? 1 : 0); return RTW_OK; }
     if (std::strcmp(name, "tonemap_blocks") == 0) { ctx->tonemap_blocks = value < 0 ? 0 : value; return RTW_OK; }
     if (std::strcmp(name, "material_variants") == 0) { ctx->material_variants = value ? 1 : 0; return RTW_OK; }
@@ -2498,6 +2502,24 @@ int rtw_render_occlusion(rtw_scene* scene, rtw_features* f, const rtw_occlusion_
 // ---- direct lighting from the feature buffers (rtw_lighting_kernels.h; the formula is rtwin.h's) --------------------------------------------
 static_assert(sizeof(rtw_light) == sizeof(RtwLight) && sizeof(rtw_light) == 36, "rtw_light travels as RtwLight");
 static_assert(RTW_LIGHT_POINT == RTW_LT_POINT && RTW_LIGHT_DIRECTIONAL == RTW_LT_DIRECTIONAL && RTW_LIGHT_INVERSE_SQUARE == RTW_LT_INVERSE_SQUARE, "light constants");
+// what rtw_render_lighting and rtw_render_indirect refuse in a light record
+static int check_lights(const rtw_light* lights, int n_lights)
+{
+    for (int j = 0; j < n_lights; j++) {
+        const rtw_light& l = lights[j];
+        if (l.type != RTW_LIGHT_POINT && l.type != RTW_LIGHT_DIRECTIONAL) return fail(RTW_ERR_INVALID, "unknown light type");
+        if (l.flags & ~RTW_LIGHT_INVERSE_SQUARE) return fail(RTW_ERR_INVALID, "unknown light flag bits");
+        for (int k = 0; k < 3; k++) if (!std::isfinite(l.v[k]) || !std::isfinite(l.color[k])) return fail(RTW_ERR_INVALID, "a light's v and color must be finite");
+        if (!std::isfinite(l.radius) || l.radius < 0.0f) return fail(RTW_ERR_INVALID, "a light's radius must be finite and not negative");
+        if (l.type == RTW_LIGHT_DIRECTIONAL) {
+            if (l.flags & RTW_LIGHT_INVERSE_SQUARE) return fail(RTW_ERR_INVALID, "a directional light has no falloff");
+            const float sq = l.v[0] * l.v[0] + l.v[1] * l.v[1] + l.v[2] * l.v[2];
+            if (!(std::fabs(sq - 1.0f) <= 1e-3f)) return fail(RTW_ERR_INVALID, "a directional light's v must be a unit vector");
+        }
+    }
+    return RTW_OK;
+}
+
 int rtw_lighting_default_params(rtw_lighting_params* p)
 {
     if (!p) return fail(RTW_ERR_INVALID, "null");
@@ -2516,18 +2538,7 @@ int rtw_render_lighting(rtw_scene* scene, rtw_features* f, const rtw_light* ligh
     if (!(p->bias >= 0.0f)) return fail(RTW_ERR_INVALID, "bias must not be negative");
     if (p->flags & ~RTW_LIGHTING_ALBEDO) return fail(RTW_ERR_INVALID, "unknown flag bits");
     if (n_passes < 1 || first_pass < 0 || (int64_t)first_pass + n_passes > ((int64_t)1 << 24)) return fail(RTW_ERR_INVALID, "need n_passes >= 1, first_pass >= 0 and first_pass + n_passes <= 2^24");
-    for (int j = 0; j < n_lights; j++) {
-        const rtw_light& l = lights[j];
-        if (l.type != RTW_LIGHT_POINT && l.type != RTW_LIGHT_DIRECTIONAL) return fail(RTW_ERR_INVALID, "unknown light type");
-        if (l.flags & ~RTW_LIGHT_INVERSE_SQUARE) return fail(RTW_ERR_INVALID, "unknown light flag bits");
-        for (int k = 0; k < 3; k++) if (!std::isfinite(l.v[k]) || !std::isfinite(l.color[k])) return fail(RTW_ERR_INVALID, "a light's v and color must be finite");
-        if (!std::isfinite(l.radius) || l.radius < 0.0f) return fail(RTW_ERR_INVALID, "a light's radius must be finite and not negative");
-        if (l.type == RTW_LIGHT_DIRECTIONAL) {
-            if (l.flags & RTW_LIGHT_INVERSE_SQUARE) return fail(RTW_ERR_INVALID, "a directional light has no falloff");
-            const float sq = l.v[0] * l.v[0] + l.v[1] * l.v[1] + l.v[2] * l.v[2];
-            if (!(std::fabs(sq - 1.0f) <= 1e-3f)) return fail(RTW_ERR_INVALID, "a directional light's v must be a unit vector");
-        }
-    }
+    { const int rl = check_lights(lights, n_lights); if (rl != RTW_OK) return rl; }
     const int rc = need_committed(scene); if (rc != RTW_OK) return rc;
     HIP_TRY(hipSetDevice(cx->device));
     rtw::LightingCall o;
@@ -2541,6 +2552,42 @@ int rtw_render_lighting(rtw_scene* scene, rtw_features* f, const rtw_light* ligh
     o.staged_shape = scene->facts.staged_shape; o.staged_top = scene->facts.staged_top; o.staged_all = scene->facts.staged_all;
     const hipError_t e = (hipError_t)rtw::launch_lighting(scene->d_scene, o, cx->stream);
     if (e != hipSuccess) return hip_fail(e, "lighting launch");
+    return RTW_OK;
+}
+
+// ---- one bounce of indirect light from the feature buffers (rtw_indirect_kernels.h; the formula is rtwin.h's) --------------------------------
+int rtw_indirect_default_params(rtw_indirect_params* p)
+{
+    if (!p) return fail(RTW_ERR_INVALID, "null");
+    p->bias = 1e-3f; p->samples = 4; p->flags = RTW_INDIRECT_ALBEDO;
+    return RTW_OK;
+}
+
+int rtw_render_indirect(rtw_scene* scene, rtw_features* f, const rtw_light* lights, int n_lights, const rtw_indirect_params* p, int first_pass, int n_passes, uint32_t seed, rtw_framebuffer* dst)
+{
+    if (!scene || !f || !p || !dst || (!lights && n_lights != 0)) return fail(RTW_ERR_INVALID, "null argument");
+    rtw_context* cx = scene->ctx;
+    if (f->ctx != cx || dst->ctx != cx) return fail(RTW_ERR_INVALID, "the scene and the buffers belong to different contexts");
+    if (f->width != dst->width || f->height != dst->height) return fail(RTW_ERR_INVALID, "the features and the destination differ in size");
+    if (n_lights < 0 || n_lights > RTW_LT_MAX) return fail(RTW_ERR_INVALID, "n_lights must be 0..8");
+    if (p->samples < 1 || p->samples > RTW_LT_MAX) return fail(RTW_ERR_INVALID, "samples must be 1..8");
+    if (!(p->bias >= 0.0f)) return fail(RTW_ERR_INVALID, "bias must not be negative");
+    if (p->flags & ~(RTW_INDIRECT_ALBEDO | RTW_INDIRECT_MIRROR)) return fail(RTW_ERR_INVALID, "unknown flag bits");
+    if (n_passes < 1 || first_pass < 0 || (int64_t)first_pass + n_passes > ((int64_t)1 << 24)) return fail(RTW_ERR_INVALID, "need n_passes >= 1, first_pass >= 0 and first_pass + n_passes <= 2^24");
+    { const int rl = check_lights(lights, n_lights); if (rl != RTW_OK) return rl; }
+    const int rc = need_committed(scene); if (rc != RTW_OK) return rc;
+    HIP_TRY(hipSetDevice(cx->device));
+    rtw::IndirectCall o;
+    o.geom = f->geom; o.albedo = f->albedo; o.ids = f->ids; o.accum = dst->accum; o.argb = dst->argb; o.gamma_thr = cx->d_gamma;
+    o.cam = scene->camera; o.width = dst->width; o.height = dst->height;
+    std::memset(o.lights, 0, sizeof o.lights);
+    if (n_lights > 0) std::memcpy(o.lights, lights, (size_t)n_lights * sizeof(rtw_light));
+    o.n_lights = n_lights; o.bias = p->bias; o.samples = p->samples; o.flags = p->flags;
+    o.first_pass = first_pass; o.n_passes = n_passes; o.seed = seed; o.deal = cx->indirect_deal; o.staging = cx->indirect_staging;
+    o.cu_count = cx->cu_count; o.single_mesh = scene->facts.single_mesh; o.carry = scene->texture_carry;
+    o.staged_shape = scene->facts.staged_shape; o.staged_top = scene->facts.staged_top; o.staged_all = scene->facts.staged_all;
+    const hipError_t e = (hipError_t)rtw::launch_indirect(scene->d_scene, o, cx->stream);
+    if (e != hipSuccess) return hip_fail(e, "indirect launch");
     return RTW_OK;
 }
 
